@@ -18,8 +18,8 @@ test-asan:        ## oracle + WAV reader under ASAN+UBSAN here; add the C++ host
 test-ubsan:       ## the restatement alone under UBSAN (same driver, prints the checksum)
 	$(MAKE) -s -C oracle san_driver_ubsan && oracle/san_driver_ubsan
 
-bench: build      ## one JSON line: hops/s, roofline, cpu_baseline
-	$(PY) bench.py
+bench: build      ## one JSON line: hops/s, roofline, cpu_baseline, every leg (--full)
+	$(PY) bench.py --full
 
 golden:           ## regenerate tests/golden/*.npz
 	$(PY) tests/golden/make_golden.py

@@ -11,11 +11,15 @@ the per-hop reference API is timed in `realtime`) with the percussive output wri
 steps exactly as consecutive process_next_hop calls leave it, and the samples are bit-identical to per-hop calls and
 to the oracle (tests/test_gpu_round3.py::test_headline_block_windows_vs_oracle checks this very block).
 
-Everything else in the JSON line is measured OUTSIDE the timed region of `value`, each leg between its own
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, settles the clocks (`--settle-ms`), runs the W warm-up steps, times
+the K steps, writes what the last step computed if `--dump-outputs DIR` is given, and prints the line: `value`, `ms_per_step`
+(wall time of one timed step), `config` and the roofline of the timed kernel from the timed steps' own HIP events.
+`--full` adds everything else below, measured OUTSIDE the timed region of `value`, each leg between its own
 synchronisation points:
   roofline        -- the dominant kernel of the timed region, timed with HIP events on the engine's stream
                      (zen_hip_hpr_profile): rt_fused_kernel (one workgroup per hop), priced with SURVEY 8(d)'s
-                     per-frame minimum 24*(nfft/2+1) + 8*hop bytes per hop.
+                     per-frame minimum 24*(nfft/2+1) + 8*hop bytes per hop; --full adds the tuned copy kernel's rate
+                     as its practical denominator (`device_copy_GBps`).
   roofline_median -- BASELINE's second metric: the stand-alone frequency-direction median kernel (47 taps over
                      whole rows of the 25 840 x 4096 magnitude matrix, 8 B/element).  `burst`: 10 launches inside
                      the three-kernel path (input freshly written: Infinity-Cache help); `sustained`: >= 1 s of
@@ -512,8 +516,10 @@ def block_run(zen_amd, grp, x2d, flags, M, steps, warmup, settle_ms, barrier, ho
     eng.profile(False)
     first = next(b for b in (bufs["P"], bufs["H"], bufs["R"]) if b is not None)
     chk = float(np.abs(first.download(4096)).sum())            # liveness only; bytes, not data path
+    names = {"H": "harmonic", "P": "percussive", "R": "residual"}
     return {"dt": dt, "breakdown": breakdown, "median": med, "checksum": chk, "eng": eng, "step": step,
-            "bufs": [d_in] + [b for b in bufs.values() if b is not None]}
+            "bufs": [d_in] + [b for b in bufs.values() if b is not None],
+            "outputs": {names[k]: b for k, b in bufs.items() if b is not None}}
 
 
 def free_run(run):
@@ -522,6 +528,22 @@ def free_run(run):
     for b in run["bufs"]:
         b.free()
     run["bufs"] = []
+
+
+DUMP_BYTES = 48 << 20       # --dump-outputs: bytes of samples written in all, at most
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: what the timed path computed in its last step, one `out_dir`/<name>.npy (float32) per output array.  An
+    output larger than its share of `budget` is cut to a fixed sample: the sorted positions np.unique(default_rng(0).integers(0,
+    size, share)), the same on every run of the same arguments, so that two builds can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // 4 // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        if a.size > share:
+            a = a[np.unique(np.random.default_rng(0).integers(0, a.size, share))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def fused_roofline(run, S, M, steps, n_out, kernel, copy_bw):
@@ -751,7 +773,8 @@ def sse_rooflines(prof, steps, frames, nfft, hop):
             "note": "dominant kernel of the step by HIP-event time"}, out
 
 
-def offline_batch_run(zen_amd, zdist, grp, rank, world, C, clip_seconds, steps, warmup, settle_ms, barrier, rooflines=True):
+def offline_batch_run(zen_amd, zdist, grp, rank, world, C, clip_seconds, steps, warmup, settle_ms, barrier, rooflines=True,
+                      dump_dir=None):
     """BASELINE configs[3]: C clips per GPU, clips sharded over the ranks, both passes resident in HBM."""
     n = int(clip_seconds * FS)
     hop_h, hop_p = 4096, 256
@@ -783,6 +806,8 @@ def offline_batch_run(zen_amd, zdist, grp, rank, world, C, clip_seconds, steps, 
     prof = eng.profile_get_all()
     eng.profile(False)
     chk, ranks = grp.sum([float(np.abs(d_p.download(4096)).sum()), 1.0])
+    if dump_dir:
+        dump_outputs(dump_dir, {"harmonic": d_h.download(), "percussive": d_p.download()})
     res = {"metric": "hops/sec (HPR-I offline, hops of both passes)", "unit": "hops/s",
            "value": world * C * (n1 + n2) * steps / dt, "ms_per_step": 1e3 * dt / steps, "steps": steps, "warmup": warmup,
            "x_realtime": world * C * clip_seconds * steps / dt, "ranks_reported": int(round(ranks)),
@@ -806,7 +831,7 @@ def offline_batch_run(zen_amd, zdist, grp, rank, world, C, clip_seconds, steps, 
     return res, first_clip, (n1, n2)
 
 
-def offline_long_run(zen_amd, zdist, grp, rank, world, steps, warmup, settle_ms, barrier):
+def offline_long_run(zen_amd, zdist, grp, rank, world, steps, warmup, settle_ms, barrier, dump_dir=None):
     """BASELINE configs[2]: one 10-minute stereo clip = 2 mono channels, HPR-I 4096/256, soft mask p = 2.  N > 1: every
     channel is cut into N time ranges, rank r computes range r of both channels from its own halo of
     input; strong scaling, no exchange."""
@@ -843,6 +868,8 @@ def offline_long_run(zen_amd, zdist, grp, rank, world, steps, warmup, settle_ms,
     prof = eng.profile_get_all()
     eng.profile(False)
     chk, ranks = grp.sum([float(np.abs(d_p.download(min(4096, max(e - b, 1)))).sum()), 1.0])
+    if dump_dir:            # (both channels go through the same output rows: the last step leaves the second channel's)
+        dump_outputs(dump_dir, {"harmonic": d_h.download(max(e - b, 0)), "percussive": d_p.download(max(e - b, 0))})
     res = {"metric": "hops/sec (HPR-I offline, hops of both passes)", "unit": "hops/s", "scaling": "strong",
            "value": 2 * (n1 + n2) * steps / dt, "ms_per_step": 1e3 * dt / steps, "steps": steps, "warmup": warmup,
            "x_realtime": 600.0 * steps / dt, "ranks_reported": int(round(ranks)),
@@ -1017,10 +1044,10 @@ def cpp_process_ms(seconds, reps=3):
         return {"error": str(exc)[:200]}
 
 
-def offline_host_run(zen_amd, seconds=3600.0, reps=4, cpu_baseline=True, variants=False):
+def offline_host_run(zen_amd, seconds=3600.0, reps=4, cpu_baseline=True, variants=False, full=True, dump_dir=None):
     """What the reference's `zen offline` times (zen/offline.h:141-147): HPRIOffline<GPU>::process on HOST vectors,
     wall clock, copies included -- zen_hip_hpri_process on a `seconds`-long mono S-music clip in plain (pageable) numpy
-    arrays, 4096/256, beta 2, hard masks.  Beside it: the link's roof measured on this box (4 B up + 8 B down per sample,
+    arrays, 4096/256, beta 2, hard masks.  Beside it (`full`): the link's roof measured on this box (4 B up + 8 B down per sample,
     pinned, both directions at once), the kernels alone on the same time ranges (resident), the C++ mirror's
     process(std::vector<float>) with its allocations, and the oracle timed the same way on a bounded sample."""
     n = int(seconds * FS)
@@ -1049,12 +1076,16 @@ def offline_host_run(zen_amd, seconds=3600.0, reps=4, cpu_baseline=True, variant
 
     main = timed()
     chk = float(np.abs(outs[1][:4096]).sum())
+    if dump_dir:
+        dump_outputs(dump_dir, {"harmonic": outs[0], "percussive": outs[1], "residual": outs[2]})
     res = {"metric": "x real time, HPRIOffline<GPU>::process on host vectors (zen/offline.h:141-147)", "unit": "x_realtime",
            "clip_seconds": seconds, "value": main["x_realtime"], "wall_ms": main["wall_ms_min"], "wall_ms_median": main["wall_ms_median"], "reps": reps,
            "hops_per_s": (n1 + n2) / (1e-3 * main["wall_ms_min"]), "host_stats": main["stats"], "checksum": chk,
            "config": {"workload": "HPRIOffline<GPU>(44100, 4096, 256, 2.0, 2.0).process on a %.0f s mono S-music clip in pageable host "
                                   "memory (numpy), three host outputs; zen_hip_hpri_process" % seconds,
                       "samples": n, "hops_pass1": n1, "hops_pass2": n2, "bytes_up": 4 * n, "bytes_down": 8 * n}}
+    if not full:
+        return res
     # ---- the serial path of rounds 1-3 (one range: up, both passes, down), same build
     res["serial_one_range"] = timed({"offline_range": 1 << 30})
     res["speedup_over_serial"] = res["serial_one_range"]["wall_ms_min"] / main["wall_ms_min"]
@@ -1233,13 +1264,17 @@ def compact_line(full):
     return line
 
 
-def emit(full, detail):
+def emit(full, detail, record=True):
     """Rank 0: the compact line on stdout; the full record to gpurun_out/bench_detail.json when that directory can be
-    written (it is what profiles/rNN_*_bench_default.json is copied from), or instead of the compact line with --detail."""
+    written (it is what profiles/rNN_*_bench_default.json is copied from), or instead of the compact line with --detail.
+    `record` False (a run without --full): the line alone, no file."""
     if detail:
         print(json.dumps(full))
         return
     line = compact_line(full)
+    if not record:
+        print(json.dumps(line))
+        return
     try:
         d = os.path.join(ROOT, "gpurun_out")
         os.makedirs(d, exist_ok=True)
@@ -1281,7 +1316,7 @@ def dry_main(args, zdist):
             "vs_baseline": None, "dtype": "f32", "data": "none",
             "config": {"workload": args.workload, "units_all_ranks": int(tot_units),
                        "units_rank0": units, "parallelism": par, "backend": "gloo"}}
-    if args.workload == "realtime_block" and world > 1 and not args.no_legs:
+    if args.full and args.workload == "realtime_block" and world > 1 and not args.no_legs:
         # the sharded offline-batch leg of the N > 1 line: every rank owns --leg-clips clips of the global batch
         mine = zdist.shard_units(args.leg_clips * world, world, rank)
         grp.barrier()
@@ -1309,7 +1344,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="realtime_block", choices=["realtime_block", "offline_batch", "offline_long", "offline_host"])
     ap.add_argument("--host-seconds", type=float, default=3600.0, help="offline_host: length of the clip")
-    ap.add_argument("--host-variants", action="store_true", help="offline_host: also time range lengths / unregistered / pinned buffers")
+    ap.add_argument("--host-variants", action="store_true",
+                    help="offline_host with --full: also time range lengths / unregistered / pinned buffers")
     ap.add_argument("--host-shard-seconds", type=float, default=600.0, help="N > 1: length of every rank's host clip in the offline_host_sharded leg")
     ap.add_argument("--hops", type=int, default=25840, help="hops per step per stream (25840 = 10 min)")
     ap.add_argument("--streams", type=int, default=1, help="independent streams per GPU")
@@ -1334,6 +1370,14 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for N > 1 (nccl = RCCL over xGMI; gloo for the CPU plumbing test)")
     ap.add_argument("--detail", action="store_true", help="print the full record (every leg's per-kernel tables) instead of the compact line")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the CPU baselines, the legs (roofline_median and the median shapes, "
+                         "all_outputs, s_noise, sse_block, offline_batch, offline_long, offline_host, block_host; the sharded legs "
+                         "for N > 1), the per-hop API, the device-copy denominator of the rooflines, offline_host's link roof and "
+                         "variants, and the detail record.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step (rank 0) as DIR/<name>.npy, "
+                         "float32; beyond %d MiB in all a fixed, seeded sample of it" % (DUMP_BYTES >> 20))
     ap.add_argument("--dry", action="store_true",
                     help="no GPU: run only the launch / sharding / aggregation plumbing with empty steps "
                          "(CPU tests; the line says dry: true and is not a measurement)")
@@ -1352,10 +1396,12 @@ def main():
     if args.dry:
         return dry_main(args, zdist)
 
-    legs = args.workload == "realtime_block" and not args.no_legs and not args.no_block_fused and args.outputs == "P" \
+    legs = args.full and args.workload == "realtime_block" and not args.no_legs and not args.no_block_fused and args.outputs == "P" \
         and args.seed_kind == "music" and args.streams == 1
+    cpu_base = args.full and not args.no_cpu_baseline
+    dump_dir = args.dump_outputs if rank == 0 else None
     cpu_all = None
-    if world == 1 and not args.no_cpu_baseline and (args.workload == "offline_batch" or legs):
+    if world == 1 and cpu_base and (args.workload == "offline_batch" or legs):
         cpu_all = cpu_baseline_offline_all_cores(4096, 256)      # forks: before anything loads or touches the GPU
     import torch
     if os.environ.get("ZEN_ALLOW_GPU_SHARING") and torch.cuda.device_count() > 0:
@@ -1395,8 +1441,10 @@ def main():
         dt, breakdown = run["dt"], run["breakdown"]
         chk, ranks = grp.sum([run["checksum"], 1.0])
         fused = breakdown["rt_fused"]["launches"] > 0
+        if dump_dir:
+            dump_outputs(dump_dir, {k: b.download() for k, b in run["outputs"].items()})
         if rank == 0:
-            copy_bw = device_copy_bandwidth(zen_amd)
+            copy_bw = device_copy_bandwidth(zen_amd) if args.full else None
             value = world * S * M * args.steps / dt
             if fused:
                 roof = fused_roofline(run, S, M, args.steps, 3 if all_out else 1, K_FUSED_HPR if all_out else K_FUSED_P, copy_bw)
@@ -1431,10 +1479,10 @@ def main():
                 # non-negativity promise: |S| >= +0), and the plain wrapper beside it for a shorter run
                 out["roofline_median"]["shapes"] = median_shapes(zen_amd, 1.0, nonneg=True)
                 out["roofline_median"]["shapes_plain"] = median_shapes(zen_amd, 0.35, nonneg=False)
-            if world == 1 and not args.no_cpu_baseline:
+            if world == 1 and cpu_base:
                 out["cpu_baseline"] = cpu_baseline_realtime(x[0])
                 out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
-            if world == 1 and not args.no_realtime:
+            if world == 1 and args.full and not args.no_realtime:
                 out["realtime"] = realtime_leg(zen_amd, x[0])
         free_run(run)
         if legs and rank == 0 and world == 1 and fused:
@@ -1503,26 +1551,27 @@ def main():
                     out["offline_host_sharded"] = oh
     elif args.workload == "offline_batch":
         res, clip0, (n1, n2) = offline_batch_run(zen_amd, zdist, grp, rank, world, args.clips, args.clip_seconds, args.steps,
-                                                 args.warmup, args.settle_ms, barrier)
+                                                 args.warmup, args.settle_ms, barrier, dump_dir=dump_dir)
         if rank == 0:
             out.update(res)
-            if world == 1 and not args.no_cpu_baseline:
+            if world == 1 and cpu_base:
                 out["cpu_baseline"] = cpu_baseline_offline(clip0, 4096, 256, n1 + n2)
                 out["cpu_baseline_all_cores"] = cpu_all
     elif args.workload == "offline_long":
-        res, ch0, (n1, n2) = offline_long_run(zen_amd, zdist, grp, rank, world, args.steps, args.warmup, args.settle_ms, barrier)
+        res, ch0, (n1, n2) = offline_long_run(zen_amd, zdist, grp, rank, world, args.steps, args.warmup, args.settle_ms, barrier,
+                                              dump_dir=dump_dir)
         if rank == 0:
             out.update(res)
-            if world == 1 and not args.no_cpu_baseline:
+            if world == 1 and cpu_base:
                 out["cpu_baseline"] = cpu_baseline_offline(ch0, 4096, 256, n1 + n2, seconds=4.0, beta=2.5, soft=True)
     elif args.workload == "offline_host":
         if rank == 0:
-            res = offline_host_run(zen_amd, args.host_seconds, max(args.leg_steps, 3), not args.no_cpu_baseline, args.host_variants)
+            res = offline_host_run(zen_amd, args.host_seconds, args.steps, cpu_base, args.host_variants, args.full, dump_dir)
             out.update(res)
             out["ms_per_step"] = res["wall_ms"]
             out["steps"], out["warmup"] = res["reps"], 1
     if rank == 0:
-        emit(out, args.detail)
+        emit(out, args.detail, record=args.full)
     grp.close()
 
 

@@ -36,12 +36,12 @@ def test_plain_launch_time_shards_and_replicas():
     j = json.loads(lines[0])
     assert j["n_gpus"] == 2 and j["scaling"] == "strong" and "time-sharded x2" in j["config"]["parallelism"]
     rc, lines, err = run([sys.executable, BENCH, "--gpus", "3", "--dry", "--backend", "gloo", "--hops", "100",
-                          "--steps", "1"])
+                          "--steps", "1", "--full"])
     assert rc == 0, err
     j = json.loads(lines[0])
     assert j["n_gpus"] == 3 and j["ranks_reported"] == 3 and j["config"]["units_all_ranks"] == 300
     assert j["config"]["parallelism"] == "replicas x3"
-    # the default N > 1 line also carries the path that shards: the offline batch, clips dealt to the ranks
+    # the --full N > 1 line also carries the path that shards: the offline batch, clips dealt to the ranks
     sh = j["offline_batch_sharded"]
     assert sh["ranks_reported"] == 3 and sh["clips_total"] == 3 * 64 and sh["clips_rank0"] == 64
     # ... and the host-clip leg (every rank HPRIOffline::process on its own host vectors at once): per-rank times gathered
@@ -112,12 +112,12 @@ def test_two_ranks_shard_clips_on_the_gpu_path():
 
 @pytest.mark.gpu
 def test_default_line_at_two_ranks_carries_the_sharded_offline_batch():
-    """`bench.py --gpus N` (what the driver runs for the scaling curve): `value` is N replicas of the realtime stream,
-    and the same line carries the sharded offline batch -- the path north_star scales -- with ranks_reported."""
+    """`bench.py --gpus N --full`: `value` is N replicas of the realtime stream, and the same line carries the sharded
+    offline batch -- the path north_star scales -- with ranks_reported."""
     env = dict(os.environ, ZEN_ALLOW_GPU_SHARING="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--backend", "gloo", "--hops", "300", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full", "--backend", "gloo", "--hops", "300", "--steps", "2", "--warmup", "1",
                         "--settle-ms", "0", "--leg-clips", "2", "--clip-seconds", "2", "--leg-steps", "2", "--host-shard-seconds", "20"],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]

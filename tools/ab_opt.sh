@@ -5,6 +5,6 @@ OPT=$1; shift
 for i in 1 2 3; do
   for v in A B; do
     if [ $v = B ]; then export ZEN_HIP_OPTIONS=$OPT; else unset ZEN_HIP_OPTIONS; fi
-    python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-realtime "$@" 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', round(d['value']/1e6,2), 'Mhops/s', {k: round(v,4) for k,v in d['kernel_ms_per_step'].items()}, (d.get('three_kernel_path') or {}).get('kernel_ms_per_step',{}).get('freq_filter'))"
+    python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-realtime "$@" 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', round(d['value']/1e6,2), 'Mhops/s', {k: round(v,4) for k,v in d['kernel_ms_per_step'].items()}, (d.get('three_kernel_path') or {}).get('kernel_ms_per_step',{}).get('freq_filter'))"
   done
 done

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: ab_opts.sh "opt1=1" "" "opt2=1,opt3=2" ...
 for o in "$@"; do
-  ZEN_HIP_OPTIONS="$o" python bench.py --workload offline_batch --steps 8 --warmup 3 --no-cpu-baseline > gpurun_out/ab_v.json 2> gpurun_out/ab_v.err || tail -3 gpurun_out/ab_v.err
+  ZEN_HIP_OPTIONS="$o" python bench.py --full --workload offline_batch --steps 8 --warmup 3 --no-cpu-baseline > /dev/null || continue
   python - "${o:-default}" <<'PY'
 import json, sys
 d = json.load(open("gpurun_out/bench_detail.json"))

@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 for v in "$@"; do
   so=zen_amd/libzen_hip${v:+_$v}.so
   [ -f "$so" ] || { echo "$so missing"; continue; }
-  ZEN_HIP_SO=$so python bench.py --workload offline_batch --steps 8 --warmup 3 --no-cpu-baseline > gpurun_out/ab_v.json 2> gpurun_out/ab_v.err || tail -3 gpurun_out/ab_v.err
+  ZEN_HIP_SO=$so python bench.py --full --workload offline_batch --steps 8 --warmup 3 --no-cpu-baseline > /dev/null || continue
   python - "${v:-base}" <<'PY'
 import json, sys
 d = json.load(open("gpurun_out/bench_detail.json"))

@@ -12,7 +12,7 @@ REV=$(cat .build_rev 2>/dev/null || echo unknown)
 echo "$REV" > $OUT/build_rev.txt
 cat .build_kernel_rev >> $OUT/build_rev.txt 2>/dev/null
 # per-kernel durations of the default bench command, legs included (the averages must agree with bench.py's HIP events)
-timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/stats --output-format csv -- python3 bench.py --no-cpu-baseline --no-realtime > $OUT/stats_run.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/stats --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-realtime > $OUT/stats_run.log 2>&1
 # (the legs start helper processes that use the GPU too -- tools/offline_host.cpp, tools/rt_latency.cpp -- and each gets a
 # stats file of its own: the one of bench.py itself is the one that holds the headline kernel)
 cp "$(grep -l 'rt_fused_kernel<12, 47, 3, true, true, true>' $(find $OUT/stats -name '*kernel_stats.csv') | head -1)" $OUT/bench_default_kernel_stats.csv
@@ -52,11 +52,11 @@ python3 tools/traffic_json.py $T "$REV" $OUT/pmc_sse_synth.json "sse_synth_kerne
 # the records bench.py quotes (traffic, valu_issue_frac) are the ones just collected: put them where it looks for them, then the lines
 cp $T profiles/${RND}_hbm_traffic.json
 cp $OUT/offline_batch_pmc.json profiles/${RND}_offline_batch_pmc.json
-python3 bench.py > $OUT/bench_default_line.json 2> $OUT/bench_default.err
+python3 bench.py --full > $OUT/bench_default_line.json 2> $OUT/bench_default.err
 cp gpurun_out/bench_detail.json $OUT/bench_default.json
-python3 bench.py --workload offline_batch --detail > $OUT/bench_offline_batch.json 2>> $OUT/bench_default.err
-python3 bench.py --workload offline_long --detail > $OUT/bench_offline_long.json 2>> $OUT/bench_default.err
-python3 bench.py --workload offline_host --host-variants --detail > $OUT/bench_offline_host.json 2>> $OUT/bench_default.err
+python3 bench.py --full --workload offline_batch --detail > $OUT/bench_offline_batch.json 2>> $OUT/bench_default.err
+python3 bench.py --full --workload offline_long --detail > $OUT/bench_offline_long.json 2>> $OUT/bench_default.err
+python3 bench.py --full --workload offline_host --host-variants --detail > $OUT/bench_offline_host.json 2>> $OUT/bench_default.err
 # BASELINE's second metric, every listed shape, the sustained protocol of the bench line (plain wrapper, then with the promise)
 python3 tools/bench_median.py --suite sustained > $OUT/median_shapes_sustained.jsonl 2>> $OUT/bench_default.err
 python3 tools/bench_median.py --suite sustained --nonneg >> $OUT/median_shapes_sustained.jsonl 2>> $OUT/bench_default.err
