@@ -336,7 +336,9 @@ int main()
 	test_demo_front_end(44100.0F, 256, 2.5F, zen::hps::OUTPUT_PERCUSSIVE, 80, 50);  // ... through the resident kernel
 	test_demo_front_end(44100.0F, 1024, 2.0F, zen::hps::OUTPUT_HARMONIC, 40, 50);
 	test_block_from_host(1024, 37);
-	test_block_from_host(256, 4500); // (several pieces of the pipeline)
+	zen_hip_set_option("host_block_hops", 512); // (the default piece, 8192 hops at hop 256, would take this block whole)
+	test_block_from_host(256, 4500);            // several pieces of the pipeline
+	zen_hip_set_option("host_block_hops", 0);
 	test_offline_long_clip();
 	std::printf("%d checks, %d failures\n", g_checks, g_fail);
 	return g_fail ? 1 : 0;

@@ -62,7 +62,6 @@ python3 tools/bench_median.py --suite sustained > $OUT/median_shapes_sustained.j
 python3 tools/bench_median.py --suite sustained --nonneg >> $OUT/median_shapes_sustained.jsonl 2>> $OUT/bench_default.err
 python3 tools/probe_lowrate.py > $OUT/lowrate_257_taps.jsonl 2>> $OUT/bench_default.err
 python3 tools/ab_block_host.py > $OUT/block_host_piece_lengths.txt 2>> $OUT/bench_default.err
-tools/ab_offline_host.sh > $OUT/offline_host_cpp_ab.txt 2>> $OUT/bench_default.err
 # micro-benchmarks the design decisions lean on
 mkdir -p /tmp/ub
 g++ -O2 -std=c++17 -I include tools/rt_latency.cpp -o /tmp/ub/rt -L zen_amd -lzen_hip -Wl,-rpath,$PWD/zen_amd && { /tmp/ub/rt 3000 --stamps; ZEN_RT_RESIDENT=100 /tmp/ub/rt 3000; } > $OUT/rt_latency.jsonl 2>&1
