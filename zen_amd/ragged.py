@@ -1,0 +1,159 @@
+"""ctypes binding of libzen_hip_ragged.so (zen_amd/ragged/zen_hip_ragged.h): the two-pass offline engine on a batch of
+clips of UNEQUAL length.  No fallback: a missing library raises.
+
+    rg = ragged.Ragged(44100.0, 4096, 256, 2.0, 2.0, n_clips=len(clips))
+    harm, perc = rg.process(clips)                      # lists of float32 arrays, one per clip, each of its clip's length
+
+    groups, fraction = ragged.plan_groups([len(c) for c in clips], 16)   # a large library: sorted groups of 16 clips
+"""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import lib as _zl
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_SO = os.environ.get("ZEN_HIP_RAGGED_SO") or os.path.join(_HERE, "libzen_hip_ragged.so")
+
+KERNELS = ("pack", "splice", "trim")
+
+# every symbol zen_amd/ragged/zen_hip_ragged.h declares: (name, restype, argtypes)
+_vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
+_psz, _pd, _pull = C.POINTER(C.c_size_t), C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
+SYMBOLS = [
+    ("zen_hip_ragged_last_error", C.c_char_p, []),
+    ("zen_hip_ragged_version", C.c_char_p, []),
+    ("zen_hip_ragged_create", _i, [_f, _sz, _sz, _f, _f, _i, _sz, C.POINTER(_vp)]),
+    ("zen_hip_ragged_destroy", _i, [_vp]),
+    ("zen_hip_ragged_set_stream", _i, [_vp, _vp]),
+    ("zen_hip_ragged_use_sse_filter", _i, [_vp]),
+    ("zen_hip_ragged_use_soft_mask", _i, [_vp]),
+    ("zen_hip_ragged_process_device", _i, [_vp, _vp, _psz, _sz, _vp, _vp, _sz]),
+    ("zen_hip_ragged_process_host", _i, [_vp, C.POINTER(_vp), _psz, C.POINTER(_vp), C.POINTER(_vp)]),
+    ("zen_hip_ragged_hop_counts", _i, [_vp, _sz, _psz, _psz]),
+    ("zen_hip_ragged_profile", _i, [_vp, _i]),
+    ("zen_hip_ragged_profile_get", _i, [_vp, _pd, _pull, _pull]),
+    ("zen_hip_ragged_profile_get_engine", _i, [_vp, _i, _pd, _pull]),
+]
+
+_lib = None
+
+
+def load():
+    """Load libzen_hip_ragged.so, building it first where it is absent (zen_amd/ragged_build.py; needs hipcc and a built
+    libzen_hip.so).  Raises if that fails."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(_SO):
+            if "ZEN_HIP_RAGGED_SO" in os.environ:
+                raise ImportError("%s does not exist" % _SO)
+            from . import ragged_build
+            ragged_build.build()
+        _zl.load()                      # the same libzen_hip.so for both bindings (found again beside this one by its rpath)
+        L = C.CDLL(_SO)
+        for name, res, args in SYMBOLS:
+            f = getattr(L, name)
+            f.restype = res
+            f.argtypes = args
+        _lib = L
+    return _lib
+
+
+def _ck(rc):
+    if rc:
+        msg = load().zen_hip_ragged_last_error().decode()
+        if rc == _zl.E_HOPS_NOT_DIVISIBLE:
+            raise _zl.ZgException(rc, msg)
+        raise _zl.ZenHipError(rc, msg)
+
+
+def _lens(lens, n_clips):
+    assert len(lens) == n_clips, "one length per clip of the handle (%d), got %d" % (n_clips, len(lens))
+    return (C.c_size_t * n_clips)(*[int(n) for n in lens])
+
+
+class Ragged:
+    """zen_hip_ragged_t: HPRIOffline on n_clips clips of unequal length per call."""
+
+    def __init__(self, fs, hop_h=4096, hop_p=256, beta_h=2.0, beta_p=2.0, nocopybord=False, n_clips=1):
+        h = C.c_void_p()
+        _ck(load().zen_hip_ragged_create(fs, hop_h, hop_p, beta_h, beta_p, int(nocopybord), n_clips, C.byref(h)))
+        self._h = h.value
+        self.n_clips = n_clips
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            load().zen_hip_ragged_destroy(self._h)
+            self._h = None
+
+    def use_sse_filter(self):
+        _ck(load().zen_hip_ragged_use_sse_filter(self._h))
+
+    def use_soft_mask(self):
+        _ck(load().zen_hip_ragged_use_soft_mask(self._h))
+
+    def set_stream(self, stream):
+        _ck(load().zen_hip_ragged_set_stream(self._h, stream))
+
+    def hop_counts(self, max_len):
+        a, b = C.c_size_t(), C.c_size_t()
+        _ck(load().zen_hip_ragged_hop_counts(self._h, max_len, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def process_device(self, audio_dev, lens, stride, harm=None, perc=None, out_stride=None):
+        """Device pointers (ints, e.g. DeviceBuffer.ptr): row c of audio_dev holds lens[c] samples; each output row gets them
+        followed by zeros up to max(lens).  Asynchronous on the handle's stream."""
+        out_stride = stride if out_stride is None else out_stride
+        _ck(load().zen_hip_ragged_process_device(self._h, audio_dev, _lens(lens, self.n_clips), stride, harm, perc, out_stride))
+
+    def process(self, clips, want=(True, True)):
+        """clips: n_clips float32 arrays of any lengths (zero included).  Returns (list_harm, list_perc): per clip an array
+        of the clip's length (None for an output that is not wanted).  Synchronous."""
+        assert len(clips) == self.n_clips, "one clip per row of the handle (%d), got %d" % (self.n_clips, len(clips))
+        clips = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1) for c in clips]
+        n = self.n_clips
+        outs = [[np.empty(c.size, np.float32) for c in clips] if w else None for w in want]
+
+        def ptrs(arrays):
+            if arrays is None:
+                return None
+            return (C.c_void_p * n)(*[a.ctypes.data if a.size else None for a in arrays])
+        _ck(load().zen_hip_ragged_process_host(self._h, ptrs(clips), _lens([c.size for c in clips], n), ptrs(outs[0]), ptrs(outs[1])))
+        return outs[0], outs[1]
+
+    def profile(self, enable=True):
+        _ck(load().zen_hip_ragged_profile(self._h, int(bool(enable))))
+
+    def profile_get(self):
+        """{"pack" | "splice" | "trim": {"ms", "bytes", "launches"}} since the last call; synchronises."""
+        ms, by, n = (C.c_double * 3)(), (C.c_ulonglong * 3)(), (C.c_ulonglong * 3)()
+        _ck(load().zen_hip_ragged_profile_get(self._h, ms, by, n))
+        return {k: {"ms": ms[i], "bytes": by[i], "launches": n[i]} for i, k in enumerate(KERNELS)}
+
+    def profile_get_engine(self):
+        """The engines' per-class kernel times, as HPRIOffline.profile_get_all."""
+        names = ("stft", "freq_filter", "time_filter", "istft", "finalize", "rt_fused")
+        out = {}
+        for ps in (1, 2):
+            ms, n = (C.c_double * 6)(), (C.c_ulonglong * 6)()
+            _ck(load().zen_hip_ragged_profile_get_engine(self._h, ps, ms, n))
+            out["pass%d" % ps] = {k: {"ms": ms[i], "launches": n[i]} for i, k in enumerate(names)}
+        return out
+
+
+def plan_groups(lengths, group):
+    """Cuts a library into batches for a Ragged handle of `group` rows: the clips sorted by length, in consecutive groups of at
+    most `group`, filled from the LONGEST clip down (the short group, if any, holds the shortest clips).  A call on a handle
+    of `group` rows costs group x (its longest clip): over all ways to put the clips into groups of at most `group`, this one
+    has the smallest sum of the groups' longest clips (its k-th group's longest clip is the (k * group + 1)-th longest of the
+    library, and no grouping can have fewer than k * group + 1 clips in groups whose maxima are at least that long).
+    Returns (groups, fraction): lists of indices into `lengths`, and sum(lengths) / sum(len(g) * longest clip of g) -- the
+    share of the padded samples that are the clips' own (1.0 for an empty library).  Pure host arithmetic."""
+    group = int(group)
+    assert group >= 1
+    order = sorted(range(len(lengths)), key=lambda i: (-int(lengths[i]), i))
+    groups = [order[i:i + group] for i in range(0, len(order), group)]
+    padded = sum(len(g) * int(lengths[g[0]]) for g in groups)
+    total = sum(int(n) for n in lengths)
+    return groups, (total / padded if padded else 1.0)
