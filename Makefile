@@ -28,4 +28,4 @@ fuzz: build       ## randomised differential test against the oracle (needs an M
 	$(PY) tools/fuzz_parity.py --seconds 120
 
 clean:
-	rm -rf zen_amd/build zen_amd/build_pcm zen_amd/build_ragged zen_amd/*.so zen_amd/bin oracle/*.so oracle/*.o oracle/san_driver_asan oracle/san_driver_ubsan tests/cpp/test_libzen tools/bin
+	rm -rf zen_amd/build zen_amd/build_pcm zen_amd/build_ragged zen_amd/build_live zen_amd/*.so zen_amd/bin oracle/*.so oracle/*.o oracle/san_driver_asan oracle/san_driver_ubsan tests/cpp/test_libzen tools/bin

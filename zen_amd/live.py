@@ -1,0 +1,190 @@
+"""ctypes binding of libzen_hip_live.so (zen_amd/live/zen_hip_live.h): the two-pass separation (HPR-I) as a stream with a
+fixed latency.  No fallback: a missing library raises.
+
+    lv = live.Live(44100.0, 4096, 256, 2.0, 2.0, max_push=4096)
+    for block in blocks:                                 # float32, any sizes
+        harm, perc, dry = lv.push(block)                 # what has become ready: lv.latency samples behind the input
+    harm, perc, dry = lv.finish()                        # the rest; together: zen offline's samples of the whole clip
+"""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import lib as _zl
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_SO = os.environ.get("ZEN_HIP_LIVE_SO") or os.path.join(_HERE, "libzen_hip_live.so")
+
+KERNELS = ("feed", "mid", "out")
+
+
+class Stats(C.Structure):
+    _fields_ = [("pushed", C.c_ulonglong), ("delivered", C.c_ulonglong), ("device_bytes", C.c_ulonglong),
+                ("allocations", C.c_ulonglong)]
+
+
+# every symbol zen_amd/live/zen_hip_live.h declares: (name, restype, argtypes)
+_vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
+_psz, _pd, _pull = C.POINTER(C.c_size_t), C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
+SYMBOLS = [
+    ("zen_hip_live_last_error", C.c_char_p, []),
+    ("zen_hip_live_version", C.c_char_p, []),
+    ("zen_hip_live_max_samples", _i, [_sz, _sz, _pull]),
+    ("zen_hip_live_create", _i, [_f, _sz, _sz, _f, _f, _i, _sz, _sz, C.POINTER(_vp)]),
+    ("zen_hip_live_destroy", _i, [_vp]),
+    ("zen_hip_live_set_stream", _i, [_vp, _vp]),
+    ("zen_hip_live_use_sse_filter", _i, [_vp]),
+    ("zen_hip_live_use_soft_mask", _i, [_vp]),
+    ("zen_hip_live_reset", _i, [_vp]),
+    ("zen_hip_live_latency", _i, [_vp, _psz]),
+    ("zen_hip_live_produces", _i, [_vp, _sz, _psz]),
+    ("zen_hip_live_pending", _i, [_vp, _psz]),
+    ("zen_hip_live_push_device", _i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _psz]),
+    ("zen_hip_live_finish_device", _i, [_vp, _vp, _vp, _vp, _sz, _psz]),
+    ("zen_hip_live_push_host", _i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _psz]),
+    ("zen_hip_live_finish_host", _i, [_vp, _vp, _vp, _vp, _sz, _psz]),
+    ("zen_hip_live_stats", _i, [_vp, C.POINTER(Stats)]),
+    ("zen_hip_live_profile", _i, [_vp, _i]),
+    ("zen_hip_live_profile_get", _i, [_vp, _pd, _pull, _pull]),
+    ("zen_hip_live_profile_get_engine", _i, [_vp, _i, _pd, _pull]),
+]
+
+_lib = None
+
+
+def load():
+    """Load libzen_hip_live.so, building it first where it is absent (zen_amd/live_build.py; needs hipcc and a built
+    libzen_hip.so).  Raises if that fails."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(_SO):
+            if "ZEN_HIP_LIVE_SO" in os.environ:
+                raise ImportError("%s does not exist" % _SO)
+            from . import live_build
+            live_build.build()
+        _zl.load()                      # the same libzen_hip.so for both bindings (found again beside this one by its rpath)
+        L = C.CDLL(_SO)
+        for name, res, args in SYMBOLS:
+            f = getattr(L, name)
+            f.restype = res
+            f.argtypes = args
+        _lib = L
+    return _lib
+
+
+def _ck(rc):
+    if rc:
+        msg = load().zen_hip_live_last_error().decode()
+        if rc == _zl.E_HOPS_NOT_DIVISIBLE:
+            raise _zl.ZgException(rc, msg)
+        raise _zl.ZenHipError(rc, msg)
+
+
+def max_samples(hop_h, hop_p):
+    """The longest stream a session of these hops accepts (the float padder's range); host arithmetic only."""
+    out = C.c_ulonglong()
+    _ck(load().zen_hip_live_max_samples(hop_h, hop_p, C.byref(out)))
+    return out.value
+
+
+class Live:
+    """zen_hip_live_t: one session of n_streams streams in lock step."""
+
+    def __init__(self, fs, hop_h=4096, hop_p=256, beta_h=2.0, beta_p=2.0, nocopybord=False, n_streams=1, max_push=0):
+        h = C.c_void_p()
+        _ck(load().zen_hip_live_create(fs, hop_h, hop_p, beta_h, beta_p, int(nocopybord), n_streams, max_push, C.byref(h)))
+        self._h = h.value
+        self.n_streams, self.hop_h, self.hop_p = n_streams, hop_h, hop_p
+        n = C.c_size_t()
+        _ck(load().zen_hip_live_latency(self._h, C.byref(n)))
+        self.latency = n.value
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            load().zen_hip_live_destroy(self._h)
+            self._h = None
+
+    def use_sse_filter(self):
+        _ck(load().zen_hip_live_use_sse_filter(self._h))
+
+    def use_soft_mask(self):
+        _ck(load().zen_hip_live_use_soft_mask(self._h))
+
+    def set_stream(self, stream):
+        _ck(load().zen_hip_live_set_stream(self._h, stream))
+
+    def reset(self):
+        _ck(load().zen_hip_live_reset(self._h))
+
+    def produces(self, m):
+        n = C.c_size_t()
+        _ck(load().zen_hip_live_produces(self._h, m, C.byref(n)))
+        return n.value
+
+    def pending(self):
+        n = C.c_size_t()
+        _ck(load().zen_hip_live_pending(self._h, C.byref(n)))
+        return n.value
+
+    def stats(self):
+        st = Stats()
+        _ck(load().zen_hip_live_stats(self._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in Stats._fields_}
+
+    def push_device(self, in_dev, m, in_stride, harm=None, perc=None, dry=None, out_stride=0):
+        """Device pointers (ints, e.g. DeviceBuffer.ptr).  Asynchronous on the handle's stream; returns the samples written to
+        each output row."""
+        n = C.c_size_t()
+        _ck(load().zen_hip_live_push_device(self._h, in_dev, m, in_stride, harm, perc, dry, out_stride, C.byref(n)))
+        return n.value
+
+    def finish_device(self, harm=None, perc=None, dry=None, out_stride=0):
+        n = C.c_size_t()
+        _ck(load().zen_hip_live_finish_device(self._h, harm, perc, dry, out_stride, C.byref(n)))
+        return n.value
+
+    def _outs(self, cnt, want):
+        shape = (cnt,) if self.n_streams == 1 else (self.n_streams, cnt)
+        return [np.empty(shape, np.float32) if w else None for w in want]
+
+    def push(self, x, want=(True, True, True)):
+        """x: float32, (m,) for one stream or (n_streams, m).  Returns (harm, perc, dry) of what has become ready, shaped like
+        x (None for an output that is not wanted).  Synchronous."""
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(self.n_streams, -1)
+        m = x.shape[1]
+        cnt = self.produces(m)
+        outs = self._outs(cnt, want)
+        n = C.c_size_t()
+        _ck(load().zen_hip_live_push_host(self._h, x.ctypes.data if m else None, m, m, *(o.ctypes.data if o is not None and cnt else None
+                                                                                          for o in outs), cnt, C.byref(n)))
+        assert n.value == cnt
+        return tuple(outs)
+
+    def finish(self, want=(True, True, True)):
+        """The rest of the stream; the session is reset.  Synchronous."""
+        cnt = self.pending()
+        outs = self._outs(cnt, want)
+        n = C.c_size_t()
+        _ck(load().zen_hip_live_finish_host(self._h, *(o.ctypes.data if o is not None and cnt else None for o in outs), cnt, C.byref(n)))
+        assert n.value == cnt
+        return tuple(outs)
+
+    def profile(self, enable=True):
+        _ck(load().zen_hip_live_profile(self._h, int(bool(enable))))
+
+    def profile_get(self):
+        """{"feed" | "mid" | "out": {"ms", "bytes", "launches"}} since the last call; synchronises."""
+        ms, by, n = (C.c_double * 3)(), (C.c_ulonglong * 3)(), (C.c_ulonglong * 3)()
+        _ck(load().zen_hip_live_profile_get(self._h, ms, by, n))
+        return {k: {"ms": ms[i], "bytes": by[i], "launches": n[i]} for i, k in enumerate(KERNELS)}
+
+    def profile_get_engine(self):
+        """The engines' per-class kernel times, as HPRIOffline.profile_get_all."""
+        names = ("stft", "freq_filter", "time_filter", "istft", "finalize", "rt_fused")
+        out = {}
+        for ps in (1, 2):
+            ms, n = (C.c_double * 6)(), (C.c_ulonglong * 6)()
+            _ck(load().zen_hip_live_profile_get_engine(self._h, ps, ms, n))
+            out["pass%d" % ps] = {k: {"ms": ms[i], "launches": n[i]} for i, k in enumerate(names)}
+        return out
