@@ -1,0 +1,173 @@
+"""ctypes binding of libzen_hip_pitch.so (zen_amd/pitch/zen_hip_pitch.h): the McLeod pitch method on chunks of rows, on the
+device.  No fallback: a missing library raises.
+
+    pt = pitch.Pitch(44100.0, 4096)
+    f0, period, clarity = pt.run(x)                      # float32 samples -> one value per chunk of 4096
+    with_hpr, without = pitch.track_hpr(x, 44100.0, 4096)  # the harmonic separation in front, all on the device
+"""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import lib as _zl
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_SO = os.environ.get("ZEN_HIP_PITCH_SO") or os.path.join(_HERE, "libzen_hip_pitch.so")
+
+KERNELS = ("pad", "fft_forward", "power", "fft_inverse", "pick")
+
+
+class Stats(C.Structure):
+    _fields_ = [("chunks", C.c_ulonglong), ("device_bytes", C.c_ulonglong), ("allocations", C.c_ulonglong)]
+
+
+# every symbol zen_amd/pitch/zen_hip_pitch.h declares: (name, restype, argtypes)
+_vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
+_pd, _pull = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
+SYMBOLS = [
+    ("zen_hip_pitch_last_error", C.c_char_p, []),
+    ("zen_hip_pitch_version", C.c_char_p, []),
+    ("zen_hip_pitch_create", _i, [_f, _sz, _sz, _sz, C.POINTER(_vp)]),
+    ("zen_hip_pitch_destroy", _i, [_vp]),
+    ("zen_hip_pitch_set_stream", _i, [_vp, _vp]),
+    ("zen_hip_pitch_run_device", _i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz]),
+    ("zen_hip_pitch_run_host", _i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz]),
+    ("zen_hip_pitch_stats", _i, [_vp, C.POINTER(Stats)]),
+    ("zen_hip_pitch_profile", _i, [_vp, _i]),
+    ("zen_hip_pitch_profile_get", _i, [_vp, _pd, _pull, _pull]),
+]
+
+_lib = None
+
+
+def load():
+    """Load libzen_hip_pitch.so, building it first where it is absent (zen_amd/pitch_build.py; needs hipcc and a built
+    libzen_hip.so).  Raises if that fails."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(_SO):
+            if "ZEN_HIP_PITCH_SO" in os.environ:
+                raise ImportError("%s does not exist" % _SO)
+            from . import pitch_build
+            pitch_build.build()
+        _zl.load()                      # the same libzen_hip.so for both bindings (found again beside this one by its rpath)
+        L = C.CDLL(_SO)
+        for name, res, args in SYMBOLS:
+            f = getattr(L, name)
+            f.restype = res
+            f.argtypes = args
+        _lib = L
+    return _lib
+
+
+def _ck(rc):
+    if rc:
+        raise _zl.ZenHipError(rc, load().zen_hip_pitch_last_error().decode())
+
+
+def _ptr(b):
+    """a DeviceBuffer, a raw device address or None"""
+    return getattr(b, "ptr", b)
+
+
+class Pitch:
+    """zen_hip_pitch_t: chunks of n samples of n_streams rows per call."""
+
+    def __init__(self, fs, n=4096, n_streams=1, max_chunks=0):
+        h = C.c_void_p()
+        _ck(load().zen_hip_pitch_create(fs, n, n_streams, max_chunks, C.byref(h)))
+        self._h = h.value
+        self.fs, self.n, self.n_streams = fs, n, n_streams
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            load().zen_hip_pitch_destroy(self._h)
+            self._h = None
+
+    def set_stream(self, stream):
+        _ck(load().zen_hip_pitch_set_stream(self._h, stream))
+
+    def stats(self):
+        st = Stats()
+        _ck(load().zen_hip_pitch_stats(self._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in Stats._fields_}
+
+    def run_device(self, in_dev, in_stride, n_chunks, step=None, pitch=None, period=None, clarity=None, nsdf=None, out_stride=0):
+        """DeviceBuffers or device addresses (ints, e.g. DeviceBuffer.offset(k)).  Asynchronous on the handle's stream."""
+        _ck(load().zen_hip_pitch_run_device(self._h, _ptr(in_dev), in_stride, n_chunks, self.n if step is None else step, _ptr(pitch),
+                                            _ptr(period), _ptr(clarity), _ptr(nsdf), out_stride))
+
+    def n_chunks(self, samples, step=None):
+        step = self.n if step is None else step
+        return 0 if samples < self.n else (samples - self.n) // step + 1
+
+    def run(self, x, step=None, nsdf=False):
+        """x: float32, (m,) for one stream or (n_streams, m); every whole chunk x[c*step : c*step + n] of it.  Returns (pitch,
+        period, clarity), each (n_chunks,) or (n_streams, n_chunks), and with nsdf=True the NSDF rows (..., n_chunks, n) as a
+        fourth.  Synchronous."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        one = x.ndim == 1
+        x = x.reshape(self.n_streams, -1)
+        m = x.shape[1]
+        step = self.n if step is None else step
+        cnt = self.n_chunks(m, step)
+        outs = [np.empty((self.n_streams, cnt), np.float32) for _ in range(3)]
+        rows = np.empty((self.n_streams, cnt, self.n), np.float32) if nsdf else None
+        _ck(load().zen_hip_pitch_run_host(self._h, x.ctypes.data if cnt else None, m, cnt, step, *(o.ctypes.data if cnt else None for o in outs),
+                                          rows.ctypes.data if nsdf and cnt else None, cnt))
+        res = outs + ([rows] if nsdf else [])
+        return tuple(r[0] if one else r for r in res)
+
+    def profile(self, enable=True):
+        _ck(load().zen_hip_pitch_profile(self._h, int(bool(enable))))
+
+    def profile_get(self):
+        """{"pad" | "fft_forward" | "power" | "fft_inverse" | "pick": {"ms", "bytes", "launches"}} since the last call; synchronises."""
+        k = len(KERNELS)
+        ms, by, n = (C.c_double * k)(), (C.c_ulonglong * k)(), (C.c_ulonglong * k)()
+        _ck(load().zen_hip_pitch_profile_get(self._h, ms, by, n))
+        return {name: {"ms": ms[i], "bytes": by[i], "launches": n[i]} for i, name in enumerate(KERNELS)}
+
+
+class HprTracker:
+    """The harmonic separation (causal, hop = n, harmonic output) and the tracker behind it, on one device buffer of two rows:
+    the samples and their harmonic part.  Sized for up to max_chunks chunks per call."""
+
+    def __init__(self, fs, n=4096, beta=2.5, max_chunks=64):
+        self.n, self.max_chunks = n, max_chunks
+        self.hpr = _zl.HPR(fs, n, beta, _zl.OUTPUT_HARMONIC, _zl.TIME_CAUSAL)
+        self.pitch = Pitch(fs, n, n_streams=2)
+        self.rows = _zl.DeviceBuffer(2 * max_chunks * n)
+        self.out = _zl.DeviceBuffer(2 * max_chunks)
+
+    def upload(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        cnt = x.size // self.n
+        assert cnt <= self.max_chunks
+        self.rows.upload(x[:cnt * self.n])
+        return cnt
+
+    def run_device(self, cnt):
+        """`cnt` chunks already in row 0 of self.rows: separation and both trackers, queued; self.out rows: without, with HPR"""
+        n, row = self.n, self.max_chunks * self.n
+        self.hpr.process(self.rows.ptr, cnt, in_stride=row, harm=self.rows.offset(row), out_stride=row)
+        self.pitch.run_device(self.rows, row, cnt, pitch=self.out, out_stride=self.max_chunks)
+
+    def download(self, cnt):
+        got = self.out.download().reshape(2, self.max_chunks)
+        return got[1, :cnt].copy(), got[0, :cnt].copy()
+
+
+def track_hpr(x, fs, n, beta=2.5):
+    """The pitch of every whole chunk of n samples of x, (with, without) the harmonic separation in front of the tracker:
+    zen_hip_hpr_process at hop n (causal, OUTPUT_HARMONIC) writes the harmonic stream into device memory and the tracker
+    reads it there."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    cnt = x.size // n
+    if cnt == 0:
+        return np.empty(0, np.float32), np.empty(0, np.float32)
+    t = HprTracker(fs, n, beta, max_chunks=cnt)
+    t.upload(x)
+    t.run_device(cnt)
+    return t.download(cnt)
