@@ -371,3 +371,40 @@ def test_past_two_to_the_24_the_stale_branches(live):
             name, diff.size, (", the first at %d" % (n - 8192 + diff[0])) if diff.size else "", int(np.sum(w[n - 8192:n] != gold[name]))))
         assert diff.size == 0, "%s: %d of the last 8192 samples differ from the oracle, the first at %d of %d" % (
             name, diff.size, n - 8192 + diff[0], n)
+
+
+# ================================================================================================ profiling
+ENGINE_CLASSES = ("stft", "freq_filter", "time_filter", "istft", "finalize", "rt_fused")
+
+
+def test_profile_counts_the_launches_and_leaves_the_outputs_alone(live, oracle):
+    """pushes of 100 / 256 / 156 samples and finish at (256, 64) are four slices: four feeds; a mid wherever pass 1 ran (not in
+    the first push, whose 100 samples stay in the carry); one out, in finish (the latency of 5760 samples is beyond the clip).
+    The counters are drained by profile_get and stay at zero while profiling is off; the rows handed out under profiling are
+    those handed out without it"""
+    x, rh, rp = reference(oracle, 256, 64, 512)
+    lv = live.Live(FS, 256, 64, 2.0, 2.0, max_push=256)
+    assert lv.latency == 5760
+    pushes = [100, 256, 156]
+    plain, _ = stream_device(lv, x, pushes)
+    lv.profile(True)
+    timed, _ = stream_device(lv, x, pushes)
+    prof = lv.profile_get()
+    print(prof)
+    assert list(prof) == list(live.KERNELS)
+    assert [p["launches"] for p in prof.values()] == [4, 3, 1]
+    for name, p in prof.items():
+        assert p["bytes"] > 0 and p["ms"] >= 0, name
+    eng = lv.profile_get_engine()
+    assert list(eng) == ["pass1", "pass2"] and all(tuple(v) == ENGINE_CLASSES for v in eng.values())
+    ms, n = (C.c_double * 6)(), (C.c_ulonglong * 6)()
+    for ps in (0, 3):
+        assert live.load().zen_hip_live_profile_get_engine(lv._h, ps, ms, n) == 2
+    zero = {"ms": 0.0, "bytes": 0, "launches": 0}
+    assert all(p == zero for p in lv.profile_get().values())
+    lv.profile(False)
+    off, _ = stream_device(lv, x, pushes)
+    assert all(p == zero for p in lv.profile_get().values())
+    for k, want in enumerate((rh, rp, x)):
+        assert np.array_equal(plain[k][0], want)
+        assert np.array_equal(timed[k], plain[k]) and np.array_equal(off[k], plain[k])

@@ -24,9 +24,10 @@ KEYS = (("H", "harm"), ("P", "perc"), ("R", "resid"))
 def pcm():
     """The library of this feature, built on demand (the session fixture of conftest.py builds the ones it links against)."""
     import zen_amd
-    from zen_amd import pcm as mod, pcm_build
-    if not os.path.exists(pcm_build.OUT):
-        pcm_build.build()
+    from zen_amd import pcm as mod
+    from zen_amd.addon_build import pcm as addon
+    if not os.path.exists(addon.OUT):
+        addon.build()
     mod.load()
     zen_amd.init(0)
     yield mod

@@ -263,11 +263,11 @@ def write_wav_float32(path, x, fs):
 
 
 def test_pitch_track_program_prints_what_track_hpr_gives(claim, tmp_path):
-    from zen_amd import pitch_build
+    from zen_amd.addon_build import pitch as addon
     x, with_hpr, without, _, _ = claim
     wav = str(tmp_path / "claim.wav")
     write_wav_float32(wav, x, 44100)
-    r = subprocess.run([pitch_build.build_demo(), wav], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
+    r = subprocess.run([addon.build_demo(), wav], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
     assert r.returncode == 0, r.stderr
     lines = r.stdout.strip().split("\n")
     assert len(lines) == 14

@@ -232,3 +232,35 @@ def test_bad_arguments_touch_nothing(ragged, oracle):
     rg.process_device(*b.args())                # the handle is still good
     zen_amd.synchronize()
     b.check(refs)
+
+
+# ================================================================================================ profiling
+ENGINE_CLASSES = ("stft", "freq_filter", "time_filter", "istft", "finalize", "rt_fused")
+
+
+def test_profile_counts_the_launches_and_leaves_the_outputs_alone(ragged, oracle):
+    """one device call with both outputs is one pack, one splice and one trim; the counters are drained by profile_get and
+    stay at zero while profiling is off; the rows written under profiling are those written without it"""
+    refs = references(oracle, 256, 64, [300, 1])
+    rg = ragged.Ragged(FS, 256, 64, 2.0, 2.0, n_clips=2)
+    plain = run_device(ragged, rg, refs)
+    rg.profile(True)
+    timed = run_device(ragged, rg, refs)
+    prof = rg.profile_get()
+    print(prof)
+    assert list(prof) == list(ragged.KERNELS)
+    for name, p in prof.items():
+        assert p["launches"] == 1 and p["bytes"] > 0 and p["ms"] >= 0, name
+    eng = rg.profile_get_engine()
+    assert list(eng) == ["pass1", "pass2"] and all(tuple(v) == ENGINE_CLASSES for v in eng.values())
+    ms, n = (C.c_double * 6)(), (C.c_ulonglong * 6)()
+    for ps in (0, 3):
+        assert ragged.load().zen_hip_ragged_profile_get_engine(rg._h, ps, ms, n) == 2
+    zero = {"ms": 0.0, "bytes": 0, "launches": 0}
+    assert all(p == zero for p in rg.profile_get().values())
+    rg.profile(False)
+    off = run_device(ragged, rg, refs)
+    assert all(p == zero for p in rg.profile_get().values())
+    for k in range(2):
+        want = plain.outs[k].download()
+        assert np.array_equal(timed.outs[k].download(), want) and np.array_equal(off.outs[k].download(), want)

@@ -108,10 +108,10 @@ def blocks_asked(n, hop):
 
 @pytest.fixture(scope="module")
 def live_so():
-    from zen_amd import live_build
-    if not os.path.exists(live_build.OUT):
-        live_build.build()
-    return live_build.OUT
+    from zen_amd.addon_build import live as addon
+    if not os.path.exists(addon.OUT):
+        addon.build()
+    return addon.OUT
 
 
 @pytest.mark.parametrize("hops", ((4096, 256), (1024, 256), (256, 64), (128, 128), (16384, 32), (768, 256), (384, 192), (300, 100)),
@@ -208,6 +208,6 @@ def test_header_compiles_as_c99(tmp_path):
 
 
 def test_kernels_add_without_contraction_or_fast_math():
-    from zen_amd import live_build
-    assert "-ffp-contract=off" in live_build.FLAGS and "-fno-fast-math" in live_build.FLAGS
-    assert not any("fast-math" in f and f != "-fno-fast-math" for f in live_build.FLAGS)
+    from zen_amd.addon_build import live as addon
+    assert "-ffp-contract=off" in addon.FLAGS and "-fno-fast-math" in addon.FLAGS
+    assert not any("fast-math" in f and f != "-fno-fast-math" for f in addon.FLAGS)

@@ -14,10 +14,10 @@ HDR = os.path.join(ROOT, "zen_amd", "pcm", "zen_hip_pcm.h")
 
 @pytest.fixture(scope="module")
 def pcm_so():
-    from zen_amd import pcm_build
-    if not os.path.exists(pcm_build.OUT):
-        pcm_build.build()
-    return pcm_build.OUT
+    from zen_amd.addon_build import pcm as addon
+    if not os.path.exists(addon.OUT):
+        addon.build()
+    return addon.OUT
 
 
 def declared_symbols():
@@ -65,9 +65,9 @@ def test_header_compiles_as_c99(tmp_path):
 
 def test_kernel_sources_keep_the_arithmetic_contract():
     """no fast-math flag, contraction off, and the rounding is not floorf(v + 0.5f)"""
-    from zen_amd import pcm_build
-    assert "-ffp-contract=off" in pcm_build.FLAGS and "-fno-fast-math" in pcm_build.FLAGS
-    assert not any("fast-math" in f and f != "-fno-fast-math" for f in pcm_build.FLAGS)
+    from zen_amd.addon_build import pcm as addon
+    assert "-ffp-contract=off" in addon.FLAGS and "-fno-fast-math" in addon.FLAGS
+    assert not any("fast-math" in f and f != "-fno-fast-math" for f in addon.FLAGS)
     conv = open(os.path.join(ROOT, "zen_amd", "pcm", "pcm_convert.h")).read()
     code = re.sub(r"/\*.*?\*/", "", conv, flags=re.S)
     assert "floorf" not in code and "__fdividef" not in code and "/ 32767.f" in code

@@ -14,10 +14,10 @@ HDR = os.path.join(ROOT, "zen_amd", "pitch", "zen_hip_pitch.h")
 
 @pytest.fixture(scope="module")
 def pitch_so():
-    from zen_amd import pitch_build
-    if not os.path.exists(pitch_build.OUT):
-        pitch_build.build()
-    return pitch_build.OUT
+    from zen_amd.addon_build import pitch as addon
+    if not os.path.exists(addon.OUT):
+        addon.build()
+    return addon.OUT
 
 
 def declared_symbols():
@@ -67,18 +67,18 @@ def test_header_compiles_as_c99(tmp_path):
 
 def test_build_keeps_the_arithmetic_contract_and_the_engines_apart():
     """no fast-math flag, contraction off; the sources see the public headers only"""
-    from zen_amd import pitch_build
-    assert "-ffp-contract=off" in pitch_build.FLAGS and "-fno-fast-math" in pitch_build.FLAGS
-    assert not any("fast-math" in f and f != "-fno-fast-math" for f in pitch_build.FLAGS)
-    for name in os.listdir(pitch_build.SRC):
-        text = open(os.path.join(pitch_build.SRC, name)).read()
+    from zen_amd.addon_build import pitch as addon
+    assert "-ffp-contract=off" in addon.FLAGS and "-fno-fast-math" in addon.FLAGS
+    assert not any("fast-math" in f and f != "-fno-fast-math" for f in addon.FLAGS)
+    for name in os.listdir(addon.SRC):
+        text = open(os.path.join(addon.SRC, name)).read()
         assert "csrc/" not in re.sub(r"//.*", "", text), name
         for inc in re.findall(r'#include "([^"]+)"', text):
-            assert inc in ("zen_hip.h", "zen_hip_pitch.h", "pitch_kernels.h", "wav.h"), (name, inc)
+            assert inc in ("zen_hip.h", "zen_hip_pitch.h", "pitch_kernels.h", "wav.h", "../addon/addon_host.h"), (name, inc)
 
 
 def test_demo_program_is_built_and_states_its_usage(pitch_so):
-    from zen_amd import pitch_build
-    exe = pitch_build.build_demo()
+    from zen_amd.addon_build import pitch as addon
+    exe = addon.build_demo()
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
     assert r.returncode == 2 and "usage: pitch-track in.wav" in r.stderr

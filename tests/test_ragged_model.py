@@ -86,10 +86,10 @@ def test_without_the_splice_the_fixture_lengths_differ(oracle):
 # ---- the boundary -----------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def ragged_so():
-    from zen_amd import ragged_build
-    if not os.path.exists(ragged_build.OUT):
-        ragged_build.build()
-    return ragged_build.OUT
+    from zen_amd.addon_build import ragged as addon
+    if not os.path.exists(addon.OUT):
+        addon.build()
+    return addon.OUT
 
 
 def declared_symbols():
@@ -134,9 +134,9 @@ def test_header_compiles_as_c99(tmp_path):
 
 
 def test_kernels_add_without_contraction_or_fast_math():
-    from zen_amd import ragged_build
-    assert "-ffp-contract=off" in ragged_build.FLAGS and "-fno-fast-math" in ragged_build.FLAGS
-    assert not any("fast-math" in f and f != "-fno-fast-math" for f in ragged_build.FLAGS)
+    from zen_amd.addon_build import ragged as addon
+    assert "-ffp-contract=off" in addon.FLAGS and "-fno-fast-math" in addon.FLAGS
+    assert not any("fast-math" in f and f != "-fno-fast-math" for f in addon.FLAGS)
 
 
 # ---- plan_groups ------------------------------------------------------------------------------------------------------------

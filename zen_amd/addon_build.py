@@ -1,0 +1,104 @@
+"""Builds the add-on libraries for gfx950 with hipcc: zen_amd/libzen_hip_<name>.so from zen_amd/<name>/, each a library of
+its own on top of libzen_hip.so's C ABI, and the demo program zen_amd/bin/pitch-track (plain g++: it reaches the GPU through
+the two C ABIs only).
+
+    python zen_amd/addon_build.py [name ...] [--force]         # no name: all of them
+
+Every library links against libzen_hip.so (zen_amd/build.py builds that one first) and finds it beside itself ($ORIGIN).
+-ffp-contract=off and no fast-math flag, for all of them: every float operation of their kernels is a single IEEE operation,
+one rounding each -- the contract of pcm/pcm_convert.h (the division, the products and the rounding are those of the host
+code in zen_amd/cli/wav.h), the one add P1 + R1 of ragged and live, and DESIGN.md section 13 for pitch.
+"""
+import glob
+import os
+import subprocess
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+BASE = os.path.join(HERE, "libzen_hip.so")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall",
+         "-I", os.path.join(ROOT, "include")]
+
+
+class Addon:
+    """One add-on: zen_amd/<name>/<sources> -> zen_amd/build_<name>/*.o -> zen_amd/libzen_hip_<name>.so.  `extra_deps`: files
+    outside its directory whose change makes its objects stale; `build_demo`: a step behind the link."""
+
+    def __init__(self, name, sources, extra_deps=(), build_demo=None, title=None):
+        self.name, self.SOURCES, self.build_demo, self.title = name, list(sources), build_demo, title or name
+        self.SRC = os.path.join(HERE, name)
+        self.OUT = os.path.join(HERE, "libzen_hip_%s.so" % name)
+        self.OBJDIR = os.path.join(HERE, "build_" + name)
+        self.FLAGS = FLAGS
+        self.extra_deps = [os.path.join(HERE, *d.split("/")) for d in extra_deps]
+
+    def deps(self):
+        hdrs = [os.path.join(self.SRC, f) for f in os.listdir(self.SRC) if f.endswith(".h")]
+        hdrs += glob.glob(os.path.join(HERE, "addon", "*.h")) + self.extra_deps
+        hdrs.append(os.path.join(ROOT, "include", "zen_hip.h"))
+        hdrs.append(os.path.abspath(__file__))   # the flags live here
+        return hdrs
+
+    def objects(self):
+        return [os.path.join(self.OBJDIR, s.replace(".hip", ".o")) for s in self.SOURCES]
+
+    def _compile(self, src):
+        obj = os.path.join(self.OBJDIR, src.replace(".hip", ".o"))
+        srcp = os.path.join(self.SRC, src)
+        newest = max(os.path.getmtime(p) for p in [srcp] + self.deps())
+        if os.path.exists(obj) and os.path.getmtime(obj) >= newest:
+            return obj, False
+        subprocess.check_call([HIPCC] + self.FLAGS + ["-c", srcp, "-o", obj])
+        return obj, True
+
+    def build(self, force=False, verbose=False):
+        """Compiles the stale objects in parallel; links where an object was compiled or libzen_hip.so is newer."""
+        if not os.path.exists(BASE):
+            raise RuntimeError("%s not built: zen_amd/build.py first (the %s library links against it)" % (BASE, self.title))
+        os.makedirs(self.OBJDIR, exist_ok=True)
+        if force:
+            for f in os.listdir(self.OBJDIR):
+                os.remove(os.path.join(self.OBJDIR, f))
+        with ThreadPoolExecutor(max_workers=len(self.SOURCES)) as ex:
+            res = list(ex.map(self._compile, self.SOURCES))
+        if any(r[1] for r in res) or not os.path.exists(self.OUT) or os.path.getmtime(self.OUT) < os.path.getmtime(BASE):
+            subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", self.OUT] + [r[0] for r in res]
+                                  + ["-L", HERE, "-lzen_hip", "-Wl,-rpath,$ORIGIN"])
+            if verbose:
+                print("built", self.OUT)
+        if self.build_demo:
+            self.build_demo(verbose)
+        return self.OUT
+
+
+DEMO = os.path.join(HERE, "bin", "pitch-track")
+
+
+def build_demo(verbose=False):
+    src, out = os.path.join(HERE, "pitch"), os.path.join(HERE, "libzen_hip_pitch.so")
+    srcs = [os.path.join(src, "pitch_track.cpp"), os.path.join(src, "zen_hip_pitch.h"), os.path.join(HERE, "cli", "wav.h"), out]
+    if os.path.exists(DEMO) and os.path.getmtime(DEMO) >= max(os.path.getmtime(p) for p in srcs):
+        return DEMO
+    os.makedirs(os.path.dirname(DEMO), exist_ok=True)
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
+                           "-I", src, "-I", os.path.join(HERE, "cli"), srcs[0], "-o", DEMO, "-L", HERE, "-lzen_hip_pitch", "-lzen_hip",
+                           "-Wl,-rpath,$ORIGIN/.."])
+    if verbose:
+        print("built", DEMO)
+    return DEMO
+
+
+pcm = Addon("pcm", ["pcm_kernels.hip", "pcm_pipe.hip"], extra_deps=["csrc/host_pipe.h"], title="PCM")
+ragged = Addon("ragged", ["ragged_kernels.hip", "ragged.hip"])
+live = Addon("live", ["live_kernels.hip", "live.hip"])
+pitch = Addon("pitch", ["pitch_kernels.hip", "pitch.hip"], build_demo=build_demo)
+ADDONS = {a.name: a for a in (pcm, ragged, live, pitch)}
+
+
+if __name__ == "__main__":
+    names = [a for a in sys.argv[1:] if not a.startswith("--")] or list(ADDONS)
+    for n in names:
+        ADDONS[n].build(force="--force" in sys.argv, verbose=True)

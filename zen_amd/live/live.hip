@@ -14,73 +14,20 @@
 // finish is the same slice with zeros for new samples, run up to padded1 / padded2 with the reference's end mapping.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <vector>
 
 #include "zen_hip_live.h"
 
+#include "../addon/hpri_pair.h"
 #include "live_kernels.h"
+
+using namespace zen_addon;
 
 namespace {
 
-thread_local char t_err[512] = "";
-
-void set_err(const char* fmt, ...)
-{
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(t_err, sizeof(t_err), fmt, ap);
-	va_end(ap);
-}
-
-#define LV_FAIL(code, ...)    \
-	do {                      \
-		set_err(__VA_ARGS__); \
-		return (code);        \
-	} while (0)
-#define LV_HIP(call)                                                                            \
-	do {                                                                                        \
-		hipError_t e__ = (call);                                                                \
-		if (e__ != hipSuccess) {                                                                \
-			set_err("%s:%d: %s failed: %s", __FILE__, __LINE__, #call, hipGetErrorString(e__)); \
-			return ZEN_HIP_E_HIP;                                                               \
-		}                                                                                       \
-	} while (0)
-// a call into libzen_hip.so: its message becomes ours
-#define LV_ZEN(call)                                        \
-	do {                                                    \
-		int rc__ = (call);                                  \
-		if (rc__ != ZEN_HIP_OK) {                           \
-			set_err("%s: %s", #call, zen_hip_last_error()); \
-			return rc__;                                    \
-		}                                                   \
-	} while (0)
-#define LV_TRY(expr)            \
-	do {                        \
-		int rc__ = (expr);      \
-		if (rc__ != ZEN_HIP_OK) \
-			return rc__;        \
-	} while (0)
-
 enum { K_FEED = 0, K_MID = 1, K_OUT = 2 };
 
-struct Timed {
-	int kernel;
-	hipEvent_t e0, e1;
-};
-
 size_t round4(size_t x) { return (x + 3) & ~(size_t)3; }
-
-// hps.cu:109-126 hpss_chunk_padder: float ceil of a float quotient, plus `lag` chunks
-size_t chunk_padder(size_t audio_size, size_t hop, size_t lag)
-{
-	const int n = (int)(ceilf((float)audio_size / (float)hop)) + (int)lag;
-	return n > 0 ? (size_t)n * hop : 0;
-}
 
 unsigned long long max_samples(size_t hop_p) // zen_hip_live.h, "The bound"
 {
@@ -92,10 +39,8 @@ unsigned long long max_samples(size_t hop_p) // zen_hip_live.h, "The bound"
 
 } // namespace
 
-struct zen_hip_live {
-	zen_hip_hpr_t e1 = nullptr; // hop_h; H, P, R; anticausal (csrc/hpri.hip:85-87)
-	zen_hip_hpr_t e2 = nullptr; // hop_p; P only; anticausal (csrc/hpri.hip:89-90)
-	size_t hop_h = 0, hop_p = 0, S = 0, lag_h = 0, lag_p = 0, sh1 = 0, sh2 = 0, max_push = 0;
+struct zen_hip_live : HpriPair {
+	size_t hop_h = 0, hop_p = 0, S = 0, sh1 = 0, sh2 = 0, max_push = 0;
 	hipStream_t stream = nullptr;
 	// rows per stream (floats): pass 1's largest slice, pass 2's, the most one call delivers, the history in front of H1
 	size_t cap1 = 0, cap2 = 0, ocap = 0, hoff = 0, row1 = 0, carry_row = 0, dry_len = 0;
@@ -106,47 +51,16 @@ struct zen_hip_live {
 	// the stream so far
 	unsigned long long pushed = 0, delivered = 0, limit = 0;
 	size_t c = 0; // samples in the carry: pushed % hop_h
-	unsigned long long device_bytes = 0, allocations = 0;
-	bool profile = false;
-	std::vector<Timed> timed;
-	double prof_ms[3] = {0, 0, 0};
-	unsigned long long prof_bytes[3] = {0, 0, 0}, prof_launches[3] = {0, 0, 0};
+	DeviceTally mem;
+	Profiler<3> prof;
 };
 
 namespace {
 
 int alloc(zen_hip_live* h, float** p, size_t floats)
 {
-	LV_ZEN(zen_hip_malloc((void**)p, sizeof(float) * floats));
-	h->device_bytes += sizeof(float) * floats;
-	h->allocations += 1;
-	return ZEN_HIP_OK;
+	return counted_malloc(&h->mem, (void**)p, sizeof(float) * floats, "zen_hip_malloc((void**)p, sizeof(float) * floats)");
 }
-
-struct KernelTimer { // HIP events around one launch of this library's kernels while profiling is on
-	zen_hip_live* h;
-	Timed t = {0, nullptr, nullptr};
-	int begin(int kernel, unsigned long long bytes)
-	{
-		if (!h->profile)
-			return ZEN_HIP_OK;
-		t.kernel = kernel;
-		LV_HIP(hipEventCreate(&t.e0));
-		LV_HIP(hipEventCreate(&t.e1));
-		LV_HIP(hipEventRecord(t.e0, h->stream));
-		h->prof_bytes[kernel] += bytes;
-		h->prof_launches[kernel] += 1;
-		return ZEN_HIP_OK;
-	}
-	int end()
-	{
-		if (!h->profile)
-			return ZEN_HIP_OK;
-		LV_HIP(hipEventRecord(t.e1, h->stream));
-		h->timed.push_back(t);
-		return ZEN_HIP_OK;
-	}
-};
 
 unsigned long long delivered_after(const zen_hip_live* h, unsigned long long pushed)
 {
@@ -156,8 +70,7 @@ unsigned long long delivered_after(const zen_hip_live* h, unsigned long long pus
 
 int reset_session(zen_hip_live* h)
 {
-	LV_ZEN(zen_hip_hpr_reset_buffers(h->e1));
-	LV_ZEN(zen_hip_hpr_reset_buffers(h->e2));
+	ZA_TRY(pair_reset_buffers(h));
 	h->pushed = h->delivered = 0;
 	h->c = 0;
 	return ZEN_HIP_OK;
@@ -196,7 +109,7 @@ int run_slice(zen_hip_live* h, const float* in_dev, size_t m, size_t in_stride, 
 		pad1 = chunk_padder((size_t)n, H, h->lag_h);
 		pad2 = chunk_padder((size_t)n, P, h->lag_p);
 		if (pad1 < s0 + sh1 || pad1 - s0 > h->cap1)
-			LV_FAIL(ZEN_HIP_E_UNSUPPORTED, "live_finish: %llu samples: pass 1 would end at %zu, %zu are done", n, pad1, s0);
+			ZA_FAIL(ZEN_HIP_E_UNSUPPORTED, "live_finish: %llu samples: pass 1 would end at %zu, %zu are done", n, pad1, s0);
 		len1 = pad1 - s0;
 		c_next = 0;
 	} else {
@@ -215,7 +128,7 @@ int run_slice(zen_hip_live* h, const float* in_dev, size_t m, size_t in_stride, 
 	const size_t d1 = fin ? (size_t)n : (size_t)delivered_after(h, h->pushed + m);
 	const size_t cnt = d1 - d0;
 	if (len2 > h->cap2 || cnt > h->ocap || len1 > h->cap1 || len2 % P != 0)
-		LV_FAIL(ZEN_HIP_E_UNSUPPORTED, "live: slice of %zu / %zu / %zu samples beyond the session's rows", len1, len2, cnt);
+		ZA_FAIL(ZEN_HIP_E_UNSUPPORTED, "live: slice of %zu / %zu / %zu samples beyond the session's rows", len1, len2, cnt);
 
 	float *hcur = h->h1[h->cur_h1], *hnext = h->h1[h->cur_h1 ^ 1];
 	zen_live::Shifted q = {h->p1, h->row1, fin ? pad1 - sh1 : NONE, fin ? pad1 : NONE, (long long)sh1 - (long long)s0, -(long long)s0};
@@ -224,7 +137,7 @@ int run_slice(zen_hip_live* h, const float* in_dev, size_t m, size_t in_stride, 
 	zen_live::Shifted sh = {hcur, h->row1, fin ? pad1 - sh1 : NONE, fin ? pad1 : NONE,
 	                        (long long)sh1 - (long long)s0 + (long long)h->hoff, -(long long)s0 + (long long)h->hoff};
 	if (!covers(q, t0, len2, len1) || !covers(sp2, d0, cnt, len2) || !covers(sh, d0, cnt, h->hoff + len1))
-		LV_FAIL(ZEN_HIP_E_UNSUPPORTED, "live: %llu samples: the end mapping leaves the rows of this slice", n);
+		ZA_FAIL(ZEN_HIP_E_UNSUPPORTED, "live: %llu samples: the end mapping leaves the rows of this slice", n);
 
 	{
 		zen_live::FeedArgs a = {};
@@ -234,26 +147,26 @@ int run_slice(zen_hip_live* h, const float* in_dev, size_t m, size_t in_stride, 
 		a.in1 = h->in1, a.in1_stride = h->cap1, a.len1 = len1;
 		a.dry = h->dry, a.dry_stride = h->dry_len, a.dry_len = h->dry_len, a.dry_pos = (size_t)(h->pushed % h->dry_len);
 		a.n_streams = S;
-		KernelTimer kt{h};
-		LV_TRY(kt.begin(K_FEED, sizeof(float) * S * (h->c + 2 * m + len1 + c_next + m)));
-		LV_HIP(zen_live::launch_feed(a, h->stream));
-		LV_TRY(kt.end());
+		auto kt = h->prof.on_stream(h->stream);
+		ZA_TRY(kt.begin(K_FEED, sizeof(float) * S * (h->c + 2 * m + len1 + c_next + m)));
+		ZA_HIP(zen_live::launch_feed(a, h->stream));
+		ZA_TRY(kt.end());
 	}
 	if (len1)
-		LV_ZEN(zen_hip_hpr_process(h->e1, h->in1, len1 / H, h->cap1, hcur + h->hoff, h->p1, h->r1, h->row1));
+		ZA_ZEN(zen_hip_hpr_process(h->e1, h->in1, len1 / H, h->cap1, hcur + h->hoff, h->p1, h->r1, h->row1));
 	if (len1 || len2) { // (len1 == 0 < len2: a finish whose pass 2 only has zeros left to read)
 		zen_live::MidArgs a = {};
 		a.p = q, a.r1 = h->r1;
 		a.in2 = h->in2, a.in2_stride = h->cap2, a.len2 = len2, a.t0 = t0;
 		a.hist_cur = hcur, a.hist_next = hnext, a.hist_stride = h->row1, a.hist_from = len1, a.hist_len = fin || !len1 ? 0 : h->hoff;
 		a.n_streams = S;
-		KernelTimer kt{h};
-		LV_TRY(kt.begin(K_MID, sizeof(float) * S * (3 * len2 + 2 * a.hist_len)));
-		LV_HIP(zen_live::launch_mid(a, h->stream));
-		LV_TRY(kt.end());
+		auto kt = h->prof.on_stream(h->stream);
+		ZA_TRY(kt.begin(K_MID, sizeof(float) * S * (3 * len2 + 2 * a.hist_len)));
+		ZA_HIP(zen_live::launch_mid(a, h->stream));
+		ZA_TRY(kt.end());
 	}
 	if (len2)
-		LV_ZEN(zen_hip_hpr_process(h->e2, h->in2, len2 / P, h->cap2, nullptr, h->p2, nullptr, h->cap2));
+		ZA_ZEN(zen_hip_hpr_process(h->e2, h->in2, len2 / P, h->cap2, nullptr, h->p2, nullptr, h->cap2));
 	if (cnt) {
 		zen_live::OutArgs a = {};
 		a.p2 = sp2, a.h1 = sh;
@@ -261,10 +174,10 @@ int run_slice(zen_hip_live* h, const float* in_dev, size_t m, size_t in_stride, 
 		a.harm_out = harm, a.perc_out = perc, a.dry_out = dry;
 		a.out_stride = out_stride, a.cnt = cnt, a.d0 = d0;
 		a.n_streams = S;
-		KernelTimer kt{h};
-		LV_TRY(kt.begin(K_OUT, sizeof(float) * S * cnt * 2 * ((harm != nullptr) + (perc != nullptr) + (dry != nullptr))));
-		LV_HIP(zen_live::launch_out(a, h->stream));
-		LV_TRY(kt.end());
+		auto kt = h->prof.on_stream(h->stream);
+		ZA_TRY(kt.begin(K_OUT, sizeof(float) * S * cnt * 2 * ((harm != nullptr) + (perc != nullptr) + (dry != nullptr))));
+		ZA_HIP(zen_live::launch_out(a, h->stream));
+		ZA_TRY(kt.end());
 	}
 	h->cur_carry ^= 1;
 	if (len1)
@@ -280,14 +193,14 @@ int check_rows(const char* who, zen_hip_live_t h, const void* in, size_t m, size
                const void* dry, size_t out_stride, size_t will_produce)
 {
 	if (m && !in)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "%s: null input", who);
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: null input", who);
 	if (((uintptr_t)in & 3) || ((uintptr_t)harm & 3) || ((uintptr_t)perc & 3) || ((uintptr_t)dry & 3))
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "%s: float pointers need 4-byte alignment", who);
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: float pointers need 4-byte alignment", who);
 	if (in_stride < m || ((harm || perc || dry) && out_stride < will_produce))
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "%s: in_stride %zu / out_stride %zu below the %zu samples pushed / %zu produced", who, in_stride,
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: in_stride %zu / out_stride %zu below the %zu samples pushed / %zu produced", who, in_stride,
 		        out_stride, m, will_produce);
 	if (h->pushed + m > h->limit)
-		LV_FAIL(ZEN_HIP_E_UNSUPPORTED, "%s: a stream of %llu samples is beyond the %llu the float padder of these hops supports", who,
+		ZA_FAIL(ZEN_HIP_E_UNSUPPORTED, "%s: a stream of %llu samples is beyond the %llu the float padder of these hops supports", who,
 		        h->pushed + (unsigned long long)m, h->limit);
 	return ZEN_HIP_OK;
 }
@@ -300,7 +213,7 @@ int push_device(zen_hip_live_t h, const float* in_dev, size_t m, size_t in_strid
 	do { // (a push of nothing is one empty slice)
 		const size_t ms = m - off < h->max_push ? m - off : h->max_push;
 		size_t got = 0;
-		LV_TRY(run_slice(h, ms ? in_dev + off : in_dev, ms, in_stride, harm ? harm + total : nullptr, perc ? perc + total : nullptr,
+		ZA_TRY(run_slice(h, ms ? in_dev + off : in_dev, ms, in_stride, harm ? harm + total : nullptr, perc ? perc + total : nullptr,
 		                 dry ? dry + total : nullptr, out_stride, false, &got));
 		total += got;
 		off += ms;
@@ -314,8 +227,8 @@ int finish_device(zen_hip_live_t h, float* harm, float* perc, float* dry, size_t
 {
 	size_t got = 0;
 	if (h->pushed)
-		LV_TRY(run_slice(h, nullptr, 0, 0, harm, perc, dry, out_stride, true, &got));
-	LV_TRY(reset_session(h));
+		ZA_TRY(run_slice(h, nullptr, 0, 0, harm, perc, dry, out_stride, true, &got));
+	ZA_TRY(reset_session(h));
 	if (produced)
 		*produced = got;
 	return ZEN_HIP_OK;
@@ -325,7 +238,7 @@ int finish_device(zen_hip_live_t h, float* harm, float* perc, float* dry, size_t
 int copy_rows(zen_hip_live* h, void* dst, size_t dst_stride, const void* src, size_t src_stride, size_t cnt, hipMemcpyKind kind)
 {
 	if (cnt)
-		LV_HIP(hipMemcpy2DAsync(dst, sizeof(float) * dst_stride, src, sizeof(float) * src_stride, sizeof(float) * cnt, h->S, kind, h->stream));
+		ZA_HIP(hipMemcpy2DAsync(dst, sizeof(float) * dst_stride, src, sizeof(float) * src_stride, sizeof(float) * cnt, h->S, kind, h->stream));
 	return ZEN_HIP_OK;
 }
 
@@ -339,9 +252,9 @@ const char* zen_hip_live_version(void) { return "zen_hip_live 1 (gfx950)"; }
 int zen_hip_live_max_samples(size_t hop_h, size_t hop_p, unsigned long long* out)
 {
 	if (!out)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "live_max_samples: null argument");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "live_max_samples: null argument");
 	if (hop_p == 0 || hop_h % hop_p != 0)
-		LV_FAIL(ZEN_HIP_E_HOPS_NOT_DIVISIBLE, "hop_h and hop_p should be evenly divisible");
+		ZA_FAIL(ZEN_HIP_E_HOPS_NOT_DIVISIBLE, "hop_h and hop_p should be evenly divisible");
 	*out = max_samples(hop_p);
 	return ZEN_HIP_OK;
 }
@@ -350,9 +263,9 @@ int zen_hip_live_create(float fs, size_t hop_h, size_t hop_p, float beta_h, floa
                         size_t max_push, zen_hip_live_t* out)
 {
 	if (!out || n_streams == 0)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "live_create: null handle or zero streams");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "live_create: null handle or zero streams");
 	if (hop_p == 0 || hop_h % hop_p != 0) // hps.cu:33-36
-		LV_FAIL(ZEN_HIP_E_HOPS_NOT_DIVISIBLE, "hop_h and hop_p should be evenly divisible");
+		ZA_FAIL(ZEN_HIP_E_HOPS_NOT_DIVISIBLE, "hop_h and hop_p should be evenly divisible");
 	zen_hip_live* h = new zen_hip_live;
 	h->hop_h = hop_h;
 	h->hop_p = hop_p;
@@ -360,14 +273,7 @@ int zen_hip_live_create(float fs, size_t hop_h, size_t hop_p, float beta_h, floa
 	h->max_push = max_push ? max_push : hop_h;
 	h->limit = max_samples(hop_p);
 	auto build = [&]() -> int {
-		LV_ZEN(zen_hip_hpr_create(fs, hop_h, beta_h, ZEN_HIP_OUTPUT_HARMONIC | ZEN_HIP_OUTPUT_PERCUSSIVE | ZEN_HIP_OUTPUT_RESIDUAL,
-		                          ZEN_HIP_TIME_ANTICAUSAL, !nocopybord, n_streams, 0, &h->e1));
-		LV_ZEN(zen_hip_hpr_create(fs, hop_p, beta_p, ZEN_HIP_OUTPUT_PERCUSSIVE, ZEN_HIP_TIME_ANTICAUSAL, !nocopybord, n_streams, 0, &h->e2));
-		zen_hip_hpr_params p1, p2;
-		LV_ZEN(zen_hip_hpr_get_params(h->e1, &p1));
-		LV_ZEN(zen_hip_hpr_get_params(h->e2, &p2));
-		h->lag_h = (size_t)p1.lag;
-		h->lag_p = (size_t)p2.lag;
+		ZA_TRY(pair_create(h, fs, hop_h, hop_p, beta_h, beta_p, nocopybord, n_streams));
 		h->sh1 = h->lag_h * hop_h;
 		h->sh2 = h->lag_p * hop_p;
 		const size_t lat = h->sh1 + h->sh2;
@@ -384,36 +290,29 @@ int zen_hip_live_create(float fs, size_t hop_h, size_t hop_p, float beta_h, floa
 		h->carry_row = round4(hop_h);
 		h->dry_len = round4(lat + hop_h + h->max_push);
 		const size_t S = n_streams;
-		LV_TRY(alloc(h, &h->carry[0], S * h->carry_row));
-		LV_TRY(alloc(h, &h->carry[1], S * h->carry_row));
-		LV_TRY(alloc(h, &h->in1, S * h->cap1));
-		LV_TRY(alloc(h, &h->h1[0], S * h->row1));
-		LV_TRY(alloc(h, &h->h1[1], S * h->row1));
-		LV_TRY(alloc(h, &h->p1, S * h->row1));
-		LV_TRY(alloc(h, &h->r1, S * h->row1));
-		LV_TRY(alloc(h, &h->in2, S * h->cap2));
-		LV_TRY(alloc(h, &h->p2, S * h->cap2));
-		LV_TRY(alloc(h, &h->dry, S * h->dry_len));
-		LV_TRY(alloc(h, &h->stage_in, S * h->max_push));
+		ZA_TRY(alloc(h, &h->carry[0], S * h->carry_row));
+		ZA_TRY(alloc(h, &h->carry[1], S * h->carry_row));
+		ZA_TRY(alloc(h, &h->in1, S * h->cap1));
+		ZA_TRY(alloc(h, &h->h1[0], S * h->row1));
+		ZA_TRY(alloc(h, &h->h1[1], S * h->row1));
+		ZA_TRY(alloc(h, &h->p1, S * h->row1));
+		ZA_TRY(alloc(h, &h->r1, S * h->row1));
+		ZA_TRY(alloc(h, &h->in2, S * h->cap2));
+		ZA_TRY(alloc(h, &h->p2, S * h->cap2));
+		ZA_TRY(alloc(h, &h->dry, S * h->dry_len));
+		ZA_TRY(alloc(h, &h->stage_in, S * h->max_push));
 		for (float*& p : h->stage_out)
-			LV_TRY(alloc(h, &p, S * h->ocap));
+			ZA_TRY(alloc(h, &p, S * h->ocap));
 		// the engines' growth up front: each runs its largest block once, on zeros
-		LV_HIP(hipMemsetAsync(h->in1, 0, sizeof(float) * S * h->cap1, h->stream));
-		LV_HIP(hipMemsetAsync(h->in2, 0, sizeof(float) * S * h->cap2, h->stream));
-		LV_ZEN(zen_hip_hpr_process(h->e1, h->in1, h->cap1 / hop_h, h->cap1, h->h1[0] + h->hoff, h->p1, h->r1, h->row1));
-		LV_ZEN(zen_hip_hpr_process(h->e2, h->in2, h->cap2 / hop_p, h->cap2, nullptr, h->p2, nullptr, h->cap2));
-		LV_TRY(reset_session(h));
-		LV_HIP(hipStreamSynchronize(h->stream));
+		ZA_HIP(hipMemsetAsync(h->in1, 0, sizeof(float) * S * h->cap1, h->stream));
+		ZA_HIP(hipMemsetAsync(h->in2, 0, sizeof(float) * S * h->cap2, h->stream));
+		ZA_ZEN(zen_hip_hpr_process(h->e1, h->in1, h->cap1 / hop_h, h->cap1, h->h1[0] + h->hoff, h->p1, h->r1, h->row1));
+		ZA_ZEN(zen_hip_hpr_process(h->e2, h->in2, h->cap2 / hop_p, h->cap2, nullptr, h->p2, nullptr, h->cap2));
+		ZA_TRY(reset_session(h));
+		ZA_HIP(hipStreamSynchronize(h->stream));
 		return ZEN_HIP_OK;
 	};
-	const int rc = build();
-	if (rc != ZEN_HIP_OK) {
-		char keep[sizeof(t_err)];
-		memcpy(keep, t_err, sizeof(keep));
-		zen_hip_live_destroy(h);
-		memcpy(t_err, keep, sizeof(keep));
-		return rc;
-	}
+	ZA_TRY(build_or_destroy(build, [&] { zen_hip_live_destroy(h); }));
 	*out = h;
 	return ZEN_HIP_OK;
 }
@@ -423,16 +322,12 @@ int zen_hip_live_destroy(zen_hip_live_t h)
 	if (!h)
 		return ZEN_HIP_OK;
 	(void)hipStreamSynchronize(h->stream);
-	zen_hip_hpr_destroy(h->e1);
-	zen_hip_hpr_destroy(h->e2);
+	pair_destroy(h);
 	float* bufs[] = {h->carry[0], h->carry[1], h->in1, h->h1[0], h->h1[1], h->p1, h->r1, h->in2, h->p2, h->dry, h->stage_in,
 	                 h->stage_out[0], h->stage_out[1], h->stage_out[2]};
 	for (float* b : bufs)
 		(void)zen_hip_free(b);
-	for (Timed& t : h->timed) {
-		(void)hipEventDestroy(t.e0);
-		(void)hipEventDestroy(t.e1);
-	}
+	h->prof.release();
 	delete h;
 	return ZEN_HIP_OK;
 }
@@ -440,10 +335,9 @@ int zen_hip_live_destroy(zen_hip_live_t h)
 int zen_hip_live_set_stream(zen_hip_live_t h, void* stream)
 {
 	if (!h)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "live_set_stream: null handle");
-	LV_ZEN(zen_hip_hpr_set_stream(h->e1, stream)); // (each waits for what the previous stream holds)
-	LV_ZEN(zen_hip_hpr_set_stream(h->e2, stream));
-	LV_HIP(hipStreamSynchronize(h->stream));
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "live_set_stream: null handle");
+	ZA_TRY(pair_set_stream(h, stream));
+	ZA_HIP(hipStreamSynchronize(h->stream));
 	h->stream = (hipStream_t)stream;
 	return ZEN_HIP_OK;
 }
@@ -451,36 +345,32 @@ int zen_hip_live_set_stream(zen_hip_live_t h, void* stream)
 int zen_hip_live_use_sse_filter(zen_hip_live_t h)
 {
 	if (!h)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
 	if (h->pushed)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "live_use_sse_filter: the stream has begun (%llu samples pushed)", h->pushed);
-	LV_ZEN(zen_hip_hpr_use_sse_filter(h->e1));
-	LV_ZEN(zen_hip_hpr_use_sse_filter(h->e2));
-	return ZEN_HIP_OK;
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "live_use_sse_filter: the stream has begun (%llu samples pushed)", h->pushed);
+	return pair_use_sse_filter(h);
 }
 
 int zen_hip_live_use_soft_mask(zen_hip_live_t h)
 {
 	if (!h)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
 	if (h->pushed)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "live_use_soft_mask: the stream has begun (%llu samples pushed)", h->pushed);
-	LV_ZEN(zen_hip_hpr_use_soft_mask(h->e1));
-	LV_ZEN(zen_hip_hpr_use_soft_mask(h->e2));
-	return ZEN_HIP_OK;
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "live_use_soft_mask: the stream has begun (%llu samples pushed)", h->pushed);
+	return pair_use_soft_mask(h);
 }
 
 int zen_hip_live_reset(zen_hip_live_t h)
 {
 	if (!h)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
 	return reset_session(h);
 }
 
 int zen_hip_live_latency(zen_hip_live_t h, size_t* samples)
 {
 	if (!h || !samples)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "live_latency: null argument");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "live_latency: null argument");
 	*samples = h->sh1 + h->sh2;
 	return ZEN_HIP_OK;
 }
@@ -488,7 +378,7 @@ int zen_hip_live_latency(zen_hip_live_t h, size_t* samples)
 int zen_hip_live_produces(zen_hip_live_t h, size_t m, size_t* out)
 {
 	if (!h || !out)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "live_produces: null argument");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "live_produces: null argument");
 	*out = (size_t)(delivered_after(h, h->pushed + m) - h->delivered);
 	return ZEN_HIP_OK;
 }
@@ -496,7 +386,7 @@ int zen_hip_live_produces(zen_hip_live_t h, size_t m, size_t* out)
 int zen_hip_live_pending(zen_hip_live_t h, size_t* out)
 {
 	if (!h || !out)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "live_pending: null argument");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "live_pending: null argument");
 	*out = (size_t)(h->pushed - h->delivered);
 	return ZEN_HIP_OK;
 }
@@ -505,8 +395,8 @@ int zen_hip_live_push_device(zen_hip_live_t h, const float* in_dev, size_t m, si
                              float* dry_dev, size_t out_stride, size_t* produced)
 {
 	if (!h)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "live_push_device: null handle");
-	LV_TRY(check_rows("live_push_device", h, in_dev, m, in_stride, harm_dev, perc_dev, dry_dev, out_stride,
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "live_push_device: null handle");
+	ZA_TRY(check_rows("live_push_device", h, in_dev, m, in_stride, harm_dev, perc_dev, dry_dev, out_stride,
 	                  (size_t)(delivered_after(h, h->pushed + m) - h->delivered)));
 	return push_device(h, in_dev, m, in_stride, harm_dev, perc_dev, dry_dev, out_stride, produced);
 }
@@ -514,8 +404,8 @@ int zen_hip_live_push_device(zen_hip_live_t h, const float* in_dev, size_t m, si
 int zen_hip_live_finish_device(zen_hip_live_t h, float* harm_dev, float* perc_dev, float* dry_dev, size_t out_stride, size_t* produced)
 {
 	if (!h)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "live_finish_device: null handle");
-	LV_TRY(check_rows("live_finish_device", h, nullptr, 0, 0, harm_dev, perc_dev, dry_dev, out_stride, (size_t)(h->pushed - h->delivered)));
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "live_finish_device: null handle");
+	ZA_TRY(check_rows("live_finish_device", h, nullptr, 0, 0, harm_dev, perc_dev, dry_dev, out_stride, (size_t)(h->pushed - h->delivered)));
 	return finish_device(h, harm_dev, perc_dev, dry_dev, out_stride, produced);
 }
 
@@ -523,8 +413,8 @@ int zen_hip_live_push_host(zen_hip_live_t h, const float* in_host, size_t m, siz
                            float* dry_host, size_t out_stride, size_t* produced)
 {
 	if (!h)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "live_push_host: null handle");
-	LV_TRY(check_rows("live_push_host", h, in_host, m, in_stride, harm_host, perc_host, dry_host, out_stride,
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "live_push_host: null handle");
+	ZA_TRY(check_rows("live_push_host", h, in_host, m, in_stride, harm_host, perc_host, dry_host, out_stride,
 	                  (size_t)(delivered_after(h, h->pushed + m) - h->delivered)));
 	float* host[3] = {harm_host, perc_host, dry_host};
 	size_t total = 0;
@@ -545,8 +435,8 @@ int zen_hip_live_push_host(zen_hip_live_t h, const float* in_host, size_t m, siz
 		off += ms;
 	} while (rc == ZEN_HIP_OK && off < m);
 	const hipError_t es = hipStreamSynchronize(h->stream); // whatever happened, nothing of this call stays in flight
-	LV_TRY(rc);
-	LV_HIP(es);
+	ZA_TRY(rc);
+	ZA_HIP(es);
 	if (produced)
 		*produced = total;
 	return ZEN_HIP_OK;
@@ -555,8 +445,8 @@ int zen_hip_live_push_host(zen_hip_live_t h, const float* in_host, size_t m, siz
 int zen_hip_live_finish_host(zen_hip_live_t h, float* harm_host, float* perc_host, float* dry_host, size_t out_stride, size_t* produced)
 {
 	if (!h)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "live_finish_host: null handle");
-	LV_TRY(check_rows("live_finish_host", h, nullptr, 0, 0, harm_host, perc_host, dry_host, out_stride, (size_t)(h->pushed - h->delivered)));
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "live_finish_host: null handle");
+	ZA_TRY(check_rows("live_finish_host", h, nullptr, 0, 0, harm_host, perc_host, dry_host, out_stride, (size_t)(h->pushed - h->delivered)));
 	float* host[3] = {harm_host, perc_host, dry_host};
 	size_t got = 0;
 	int rc = finish_device(h, host[0] ? h->stage_out[0] : nullptr, host[1] ? h->stage_out[1] : nullptr,
@@ -565,8 +455,8 @@ int zen_hip_live_finish_host(zen_hip_live_t h, float* harm_host, float* perc_hos
 		if (host[o])
 			rc = copy_rows(h, host[o], out_stride, h->stage_out[o], h->ocap, got, hipMemcpyDeviceToHost);
 	const hipError_t es = hipStreamSynchronize(h->stream);
-	LV_TRY(rc);
-	LV_HIP(es);
+	ZA_TRY(rc);
+	ZA_HIP(es);
 	if (produced)
 		*produced = got;
 	return ZEN_HIP_OK;
@@ -575,57 +465,35 @@ int zen_hip_live_finish_host(zen_hip_live_t h, float* harm_host, float* perc_hos
 int zen_hip_live_stats(zen_hip_live_t h, zen_hip_live_stats_t* out)
 {
 	if (!h || !out)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "live_stats: null argument");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "live_stats: null argument");
 	out->pushed = h->pushed;
 	out->delivered = h->delivered;
-	out->device_bytes = h->device_bytes;
-	out->allocations = h->allocations;
+	out->device_bytes = h->mem.device_bytes;
+	out->allocations = h->mem.allocations;
 	return ZEN_HIP_OK;
 }
 
 int zen_hip_live_profile(zen_hip_live_t h, int enable)
 {
 	if (!h)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
-	LV_ZEN(zen_hip_hpr_profile(h->e1, enable));
-	LV_ZEN(zen_hip_hpr_profile(h->e2, enable));
-	h->profile = enable != 0;
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
+	ZA_TRY(pair_profile(h, enable));
+	h->prof.on = enable != 0;
 	return ZEN_HIP_OK;
 }
 
 int zen_hip_live_profile_get(zen_hip_live_t h, double ms[3], unsigned long long bytes[3], unsigned long long launches[3])
 {
 	if (!h || !ms || !bytes || !launches)
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "live_profile_get: null argument");
-	hipError_t e = hipSuccess;
-	for (Timed& t : h->timed) {
-		float v = 0.f;
-		if (e == hipSuccess)
-			e = hipEventSynchronize(t.e1);
-		if (e == hipSuccess)
-			e = hipEventElapsedTime(&v, t.e0, t.e1);
-		h->prof_ms[t.kernel] += v;
-		(void)hipEventDestroy(t.e0);
-		(void)hipEventDestroy(t.e1);
-	}
-	h->timed.clear();
-	for (int k = 0; k < 3; ++k) {
-		ms[k] = h->prof_ms[k];
-		bytes[k] = h->prof_bytes[k];
-		launches[k] = h->prof_launches[k];
-		h->prof_ms[k] = 0;
-		h->prof_bytes[k] = h->prof_launches[k] = 0;
-	}
-	LV_HIP(e);
-	return ZEN_HIP_OK;
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "live_profile_get: null argument");
+	return h->prof.drain(ms, bytes, launches);
 }
 
 int zen_hip_live_profile_get_engine(zen_hip_live_t h, int pass, double ms[6], unsigned long long launches[6])
 {
 	if (!h || (pass != 1 && pass != 2))
-		LV_FAIL(ZEN_HIP_E_BAD_ARG, "live_profile_get_engine: pass must be 1 or 2");
-	LV_ZEN(zen_hip_hpr_profile_get_all(pass == 1 ? h->e1 : h->e2, ms, launches));
-	return ZEN_HIP_OK;
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "live_profile_get_engine: pass must be 1 or 2");
+	return pair_profile_get_engine(h, pass, ms, launches);
 }
 
 } // extern "C"

@@ -2,14 +2,10 @@
 // new samples into pass 1's input rows, the new carry, the dry ring), mid (pass 1's P1 + R1 into pass 2's input rows, the
 // H1 delay) and out (pass 2's output, the delayed H1 and the delayed input into the caller's rows).
 //
-// Shape of all three, as ragged_kernels.hip: blockIdx.y walks the streams, the workgroups of a stream walk a destination row
-// in a grid-stride loop over groups of 4 floats that start on a 16-byte boundary OF THE DESTINATION (global_store_dwordx4),
-// with a scalar head in front of the first boundary and a scalar tail behind the last whole group: the caller's pointers and
-// strides only promise 4-byte alignment.  A group's source is read with one global_load_dwordx4 where its address happens to
-// be 16-byte aligned too, with four dword loads otherwise.  A group that straddles a splice point (the end of the carry, the
-// start of the stream's life, the end mapping of finish, the wrap of the dry ring) is assembled sample by sample, so nothing
-// outside the source's own samples is ever read.  No LDS, no atomics.  The grid is capped at 8 workgroups of 256 threads per
-// CU (32 wavefronts, the most a CU holds).
+// Shape of all three: blockIdx.y walks the streams, the workgroups of a stream walk a destination row as
+// ../addon/row_walk.h describes (16-byte stores on the destination's boundaries, a scalar head and tail).  A group that
+// straddles a splice point (the end of the carry, the start of the stream's life, the end mapping of finish, the wrap of
+// the dry ring) is assembled sample by sample, so nothing outside the source's own samples is ever read.
 //
 // The only arithmetic is Q = P1 + R1: one IEEE binary32 add, what the engine's `add` destination and the reference's
 // sum_vectors_functor (libzen/hps.h:142-150) compute.
@@ -19,39 +15,14 @@
 
 #include "live_kernels.h"
 
+#include "../addon/row_walk.h"
+
 #pragma clang fp contract(off)
 
 namespace zen_live {
 namespace {
 
-constexpr int TPB = 256;
-
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-__device__ __forceinline__ float4 load4(const float* __restrict__ p)
-{
-	if (aligned16(p))
-		return *reinterpret_cast<const float4*>(p);
-	return make_float4(p[0], p[1], p[2], p[3]);
-}
-
-// The walk over one destination row of `len` floats: one(j) gives sample j, four(j0) the samples j0 .. j0+3 (all < len).
-template <class One, class Four>
-__device__ __forceinline__ void walk_row(float* __restrict__ dst, size_t len, size_t tid, size_t nthreads, One one, Four four)
-{
-	size_t head = ((16 - ((uintptr_t)dst & 15)) & 15) / 4; // floats in front of the first 16-byte boundary of dst
-	if (head > len)
-		head = len;
-	const size_t n_groups = (len - head) / 4, tail = head + n_groups * 4;
-	for (size_t j = tid; j < head; j += nthreads)
-		dst[j] = one(j);
-	for (size_t j = tail + tid; j < len; j += nthreads)
-		dst[j] = one(j);
-	for (size_t g = tid; g < n_groups; g += nthreads) {
-		const size_t j0 = head + g * 4;
-		*reinterpret_cast<float4*>(dst + j0) = four(j0);
-	}
-}
+using namespace zen_addon;
 
 // X[x] of X = carry[0, c) ++ in[0, m) ++ zeros
 __device__ __forceinline__ float concat1(const float* __restrict__ carry, size_t c, const float* __restrict__ in, size_t m, size_t x)
@@ -200,27 +171,6 @@ __global__ __launch_bounds__(TPB) void out_kernel(OutArgs a)
 			walk_row(a.dry_out + s * a.out_stride, a.cnt, tid, nthreads, one, four);
 		}
 	}
-}
-
-// gx workgroups per stream x gy streams: enough to cover a row of `len` floats, at most 8 workgroups per CU over the grid
-dim3 grid_for(size_t len, size_t n_streams)
-{
-	static unsigned cap = 0;
-	if (!cap) {
-		int dev = 0, cus = 0;
-		if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-			cus = 256;
-		(void)hipGetLastError();
-		cap = 8u * (unsigned)cus;
-	}
-	const unsigned gy = (unsigned)(n_streams < 65535 ? n_streams : 65535);
-	size_t gx = ((len + 3) / 4 + TPB - 1) / TPB;
-	const size_t gx_cap = cap / gy > 0 ? cap / gy : 1;
-	if (gx > gx_cap)
-		gx = gx_cap;
-	if (gx < 1)
-		gx = 1;
-	return dim3((unsigned)gx, gy, 1);
 }
 
 size_t max3(size_t a, size_t b, size_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }

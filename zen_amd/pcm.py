@@ -9,14 +9,11 @@ HPR, HPRIOffline; HPRRealtime through its p_impl) and numpy int16 arrays.  No fa
     pcm.release(eng)                                            # before the engine goes
 """
 import ctypes as C
-import os
 
 import numpy as np
 
+from . import _addon
 from . import lib as _zl
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.environ.get("ZEN_HIP_PCM_SO") or os.path.join(_HERE, "libzen_hip_pcm.so")
 
 PEAK, GAIN = 0, 1
 
@@ -42,28 +39,13 @@ SYMBOLS = [
     ("zen_hip_pcm_release_all", _i, []),
 ]
 
-_lib = None
-
-
 def load():
-    """Load libzen_hip_pcm.so (built by zen_amd/pcm_build.py or __graft_entry__.build()).  Raises if absent."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO):
-            raise ImportError("%s not built: run `python zen_amd/pcm_build.py` (needs hipcc)" % _SO)
-        _zl.load()                      # the same libzen_hip.so for both bindings (found again beside this one by its rpath)
-        L = C.CDLL(_SO)
-        for name, res, args in SYMBOLS:
-            f = getattr(L, name)
-            f.restype = res
-            f.argtypes = args
-        _lib = L
-    return _lib
+    """Load libzen_hip_pcm.so, building it first where it is absent (_addon.load).  Raises if that fails."""
+    return _addon.load("pcm", SYMBOLS)
 
 
 def _ck(rc):
-    if rc:
-        raise _zl.ZenHipError(rc, load().zen_hip_pcm_last_error().decode())
+    _addon.check(rc, load().zen_hip_pcm_last_error)
 
 
 def _handle(engine):

@@ -10,7 +10,7 @@
  * |x * 32767| < 32767.5 the two agree bit for bit.
  *
  * Every product and quotient below is rounded to binary32 on its own.  Files that include this header are compiled with
- * -ffp-contract=off and without any fast-math flag (zen_amd/pcm_build.py); the pragma below says the same to clang.
+ * -ffp-contract=off and without any fast-math flag (zen_amd/addon_build.py); the pragma below says the same to clang.
  */
 #ifndef ZEN_PCM_CONVERT_H
 #define ZEN_PCM_CONVERT_H

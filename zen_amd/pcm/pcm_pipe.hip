@@ -9,8 +9,6 @@
 
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <thread>
@@ -19,53 +17,17 @@
 
 #include "zen_hip_pcm.h"
 
+#include "../addon/addon_host.h"
 #include "../csrc/host_pipe.h" // host_pinned, Registered: shared with the float pipelines
 #include "pcm_convert.h"
 #include "pcm_kernels.h"
 
+using namespace zen_addon;
 using zen_hip_impl::Registered;
 
 namespace {
 
-thread_local char t_err[512] = "";
 thread_local zen_hip_pcm_host_stats t_stats = {};
-
-void set_err(const char* fmt, ...)
-{
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(t_err, sizeof(t_err), fmt, ap);
-	va_end(ap);
-}
-
-#define PF_FAIL(code, ...)    \
-	do {                      \
-		set_err(__VA_ARGS__); \
-		return (code);        \
-	} while (0)
-#define PF_HIP(call)                                                                                  \
-	do {                                                                                              \
-		hipError_t e__ = (call);                                                                      \
-		if (e__ != hipSuccess) {                                                                      \
-			set_err("%s:%d: %s failed: %s", __FILE__, __LINE__, #call, hipGetErrorString(e__));       \
-			return ZEN_HIP_E_HIP;                                                                     \
-		}                                                                                             \
-	} while (0)
-// a call into libzen_hip.so: its message becomes ours
-#define PF_ZEN(call)                                        \
-	do {                                                    \
-		int rc__ = (call);                                  \
-		if (rc__ != ZEN_HIP_OK) {                           \
-			set_err("%s: %s", #call, zen_hip_last_error()); \
-			return rc__;                                    \
-		}                                                   \
-	} while (0)
-#define PF_TRY(expr)            \
-	do {                        \
-		int rc__ = (expr);      \
-		if (rc__ != ZEN_HIP_OK) \
-			return rc__;        \
-	} while (0)
 
 double now_ms()
 {
@@ -104,15 +66,15 @@ int ctx_for(void* handle, int kind, Ctx** out)
 		c = new Ctx;
 	c->kind = kind; // (a context left behind by a destroyed engine whose address a new handle took over serves that one)
 	if (!c->run)
-		PF_HIP(hipStreamCreateWithFlags(&c->run, hipStreamNonBlocking));
+		ZA_HIP(hipStreamCreateWithFlags(&c->run, hipStreamNonBlocking));
 	if (!c->s_in)
-		PF_HIP(hipStreamCreateWithFlags(&c->s_in, hipStreamNonBlocking));
+		ZA_HIP(hipStreamCreateWithFlags(&c->s_in, hipStreamNonBlocking));
 	if (!c->s_out)
-		PF_HIP(hipStreamCreateWithFlags(&c->s_out, hipStreamNonBlocking));
+		ZA_HIP(hipStreamCreateWithFlags(&c->s_out, hipStreamNonBlocking));
 	if (!c->minmax)
-		PF_ZEN(zen_hip_malloc((void**)&c->minmax, 6 * sizeof(float)));
+		ZA_ZEN(zen_hip_malloc((void**)&c->minmax, 6 * sizeof(float)));
 	if (!c->minmax_host)
-		PF_ZEN(zen_hip_host_alloc_mapped(6 * sizeof(float), 0, (void**)&c->minmax_host, (void**)&c->minmax_host_dev));
+		ZA_ZEN(zen_hip_host_alloc_mapped(6 * sizeof(float), 0, (void**)&c->minmax_host, (void**)&c->minmax_host_dev));
 	*out = c;
 	return ZEN_HIP_OK;
 }
@@ -120,9 +82,9 @@ int ctx_for(void* handle, int kind, Ctx** out)
 int sync_all(Ctx* c)
 {
 	const hipError_t a = hipStreamSynchronize(c->s_out), b = hipStreamSynchronize(c->run), d = hipStreamSynchronize(c->s_in);
-	PF_HIP(a);
-	PF_HIP(b);
-	PF_HIP(d);
+	ZA_HIP(a);
+	ZA_HIP(b);
+	ZA_HIP(d);
 	return ZEN_HIP_OK;
 }
 
@@ -131,11 +93,11 @@ int grow(Ctx* c, T*& p, size_t& cap, size_t want)
 {
 	if (want <= cap)
 		return ZEN_HIP_OK;
-	PF_TRY(sync_all(c));
+	ZA_TRY(sync_all(c));
 	(void)zen_hip_free(p);
 	p = nullptr; // a failed allocation below must not leave a freed pointer behind a stale capacity
 	cap = 0;
-	PF_ZEN(zen_hip_malloc((void**)&p, sizeof(T) * want));
+	ZA_ZEN(zen_hip_malloc((void**)&p, sizeof(T) * want));
 	cap = want;
 	return ZEN_HIP_OK;
 }
@@ -144,7 +106,7 @@ int need_events(Ctx* c, size_t n)
 {
 	while (c->ev.size() < n) {
 		hipEvent_t e;
-		PF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+		ZA_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
 		c->ev.push_back(e);
 	}
 	return ZEN_HIP_OK;
@@ -230,9 +192,9 @@ void zero_host(int16_t* dst, size_t n)
 int check_mode_channels(const char* who, int channels, int mode)
 {
 	if (channels != 1 && channels != 2)
-		PF_FAIL(ZEN_HIP_E_BAD_ARG, "%s: channels must be 1 or 2 (got %d)", who, channels);
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: channels must be 1 or 2 (got %d)", who, channels);
 	if (mode != ZEN_HIP_PCM_PEAK && mode != ZEN_HIP_PCM_GAIN)
-		PF_FAIL(ZEN_HIP_E_BAD_ARG, "%s: mode must be ZEN_HIP_PCM_PEAK or ZEN_HIP_PCM_GAIN (got %d)", who, mode);
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: mode must be ZEN_HIP_PCM_PEAK or ZEN_HIP_PCM_GAIN (got %d)", who, mode);
 	return ZEN_HIP_OK;
 }
 
@@ -248,14 +210,14 @@ const char* zen_hip_pcm_version(void) { return "zen_hip_pcm 1 (gfx950)"; }
 int zen_hip_pcm_to_float(const int16_t* src_dev, int channels, size_t n_frames, float* dst_dev, void* stream)
 {
 	if (channels != 1 && channels != 2)
-		PF_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_to_float: channels must be 1 or 2 (got %d)", channels);
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_to_float: channels must be 1 or 2 (got %d)", channels);
 	if (n_frames == 0)
 		return ZEN_HIP_OK;
 	if (!src_dev || !dst_dev)
-		PF_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_to_float: null argument");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_to_float: null argument");
 	if (((uintptr_t)src_dev & 1) || ((uintptr_t)dst_dev & 3))
-		PF_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_to_float: int16_t pointers need 2-byte, float pointers 4-byte alignment");
-	PF_HIP(zen_pcm::launch_to_float(src_dev, channels, n_frames, dst_dev, (hipStream_t)stream));
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_to_float: int16_t pointers need 2-byte, float pointers 4-byte alignment");
+	ZA_HIP(zen_pcm::launch_to_float(src_dev, channels, n_frames, dst_dev, (hipStream_t)stream));
 	return ZEN_HIP_OK;
 }
 
@@ -264,10 +226,10 @@ int zen_hip_pcm_peak(const float* src_dev, size_t n, float* minmax_dev, void* st
 	if (n == 0)
 		return ZEN_HIP_OK;
 	if (!src_dev || !minmax_dev)
-		PF_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_peak: null argument");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_peak: null argument");
 	if (((uintptr_t)src_dev & 3) || ((uintptr_t)minmax_dev & 3))
-		PF_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_peak: float pointers need 4-byte alignment");
-	PF_HIP(zen_pcm::launch_peak(src_dev, n, minmax_dev, (hipStream_t)stream));
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_peak: float pointers need 4-byte alignment");
+	ZA_HIP(zen_pcm::launch_peak(src_dev, n, minmax_dev, (hipStream_t)stream));
 	return ZEN_HIP_OK;
 }
 
@@ -275,21 +237,21 @@ int zen_hip_pcm_from_float(const float* src_dev, size_t n, int mode, float gain,
                            void* stream)
 {
 	if (mode != ZEN_HIP_PCM_PEAK && mode != ZEN_HIP_PCM_GAIN)
-		PF_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_from_float: mode must be ZEN_HIP_PCM_PEAK or ZEN_HIP_PCM_GAIN (got %d)", mode);
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_from_float: mode must be ZEN_HIP_PCM_PEAK or ZEN_HIP_PCM_GAIN (got %d)", mode);
 	if (n == 0)
 		return ZEN_HIP_OK;
 	if (!src_dev || !dst_dev || (mode == ZEN_HIP_PCM_PEAK && !minmax_dev))
-		PF_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_from_float: null argument");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_from_float: null argument");
 	if (((uintptr_t)src_dev & 3) || ((uintptr_t)dst_dev & 1) || ((uintptr_t)minmax_dev & 3))
-		PF_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_from_float: int16_t pointers need 2-byte, float pointers 4-byte alignment");
-	PF_HIP(zen_pcm::launch_from_float(src_dev, n, mode, gain, minmax_dev, dst_dev, (hipStream_t)stream));
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_from_float: int16_t pointers need 2-byte, float pointers 4-byte alignment");
+	ZA_HIP(zen_pcm::launch_from_float(src_dev, n, mode, gain, minmax_dev, dst_dev, (hipStream_t)stream));
 	return ZEN_HIP_OK;
 }
 
 int zen_hip_pcm_host_stats_get(zen_hip_pcm_host_stats* out)
 {
 	if (!out)
-		PF_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_host_stats_get: null argument");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_host_stats_get: null argument");
 	*out = t_stats;
 	return ZEN_HIP_OK;
 }
@@ -333,12 +295,12 @@ int zen_hip_pcm_hpr_process_host(zen_hip_hpr_t h, const int16_t* in_host, int ch
                                  int16_t* resid, int mode, float gain, float peaks[3], size_t piece_hops)
 {
 	if (!h || !in_host)
-		PF_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpr_process_host: null argument");
-	PF_TRY(check_mode_channels("pcm_hpr_process_host", channels, mode));
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpr_process_host: null argument");
+	ZA_TRY(check_mode_channels("pcm_hpr_process_host", channels, mode));
 	zen_hip_hpr_params P;
-	PF_ZEN(zen_hip_hpr_get_params(h, &P));
+	ZA_ZEN(zen_hip_hpr_get_params(h, &P));
 	if (P.n_streams != 1)
-		PF_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpr_process_host: one stream per engine (host blocks of several streams: one engine each)");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpr_process_host: one stream per engine (host blocks of several streams: one engine each)");
 	if (n_hops == 0)
 		return ZEN_HIP_OK;
 	const size_t hop = P.hop, n = n_hops * hop, ch = (size_t)channels;
@@ -346,18 +308,18 @@ int zen_hip_pcm_hpr_process_host(zen_hip_hpr_t h, const int16_t* in_host, int ch
 	{
 		const Span s[4] = {{(const char*)in_host, 2 * ch * n}, {(const char*)harm, 2 * n}, {(const char*)perc, 2 * n}, {(const char*)resid, 2 * n}};
 		if (any_overlap(s, 4))
-			PF_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpr_process_host: the host buffers must not overlap (pieces come down while later pieces go up)");
+			ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpr_process_host: the host buffers must not overlap (pieces come down while later pieces go up)");
 	}
 	const double t_start = now_ms();
 	Ctx* c = nullptr;
-	PF_TRY(ctx_for(h, KIND_HPR, &c));
-	PF_ZEN(zen_hip_hpr_set_stream(h, c->run));
-	PF_TRY(grow(c, c->in16, c->in16_cap, n * ch));
-	PF_TRY(grow(c, c->fin, c->fin_cap, n));
+	ZA_TRY(ctx_for(h, KIND_HPR, &c));
+	ZA_ZEN(zen_hip_hpr_set_stream(h, c->run));
+	ZA_TRY(grow(c, c->in16, c->in16_cap, n * ch));
+	ZA_TRY(grow(c, c->fin, c->fin_cap, n));
 	for (int o = 0; o < 3; ++o)
 		if (hosts[o]) {
-			PF_TRY(grow(c, c->fout[o], c->fout_cap[o], n));
-			PF_TRY(grow(c, c->out16[o], c->out16_cap[o], n));
+			ZA_TRY(grow(c, c->fout[o], c->fout_cap[o], n));
+			ZA_TRY(grow(c, c->out16[o], c->out16_cap[o], n));
 		}
 	// default pieces: 4 Mi samples in GAIN mode -- 8 MiB on the link per piece and direction, the float path's rule in bytes --
 	// and 8 Mi in PEAK mode, where nothing comes down inside the loop and the pieces only pace the uploads and the tail
@@ -372,7 +334,7 @@ int zen_hip_pcm_hpr_process_host(zen_hip_hpr_t h, const int16_t* in_host, int ch
 	const size_t n_pieces = ceil_div(n_hops, piece);
 	// events: [k] piece k is up and widened, [n_pieces + k] piece k is through the engine (PEAK: and folded into min / max),
 	// [2 n_pieces + k] PEAK: piece k is narrowed, [3 n_pieces] PEAK: the peaks are known
-	PF_TRY(need_events(c, 3 * n_pieces + 1));
+	ZA_TRY(need_events(c, 3 * n_pieces + 1));
 	Registered reg_in, reg_out[3];
 	reg_in.take(in_host, 2 * ch * n, true);
 	for (int o = 0; o < 3; ++o)
@@ -391,56 +353,56 @@ int zen_hip_pcm_hpr_process_host(zen_hip_hpr_t h, const int16_t* in_host, int ch
 	auto upload = [&](size_t k) -> int {
 		size_t b, m;
 		span_of(k, &b, &m);
-		PF_HIP(hipMemcpyAsync(c->in16 + b * ch, in_host + b * ch, 2 * ch * m * hop, hipMemcpyHostToDevice, c->s_in));
-		PF_HIP(zen_pcm::launch_to_float(c->in16 + b * ch, channels, m * hop, c->fin + b, c->s_in));
-		PF_HIP(hipEventRecord(c->ev[k], c->s_in));
+		ZA_HIP(hipMemcpyAsync(c->in16 + b * ch, in_host + b * ch, 2 * ch * m * hop, hipMemcpyHostToDevice, c->s_in));
+		ZA_HIP(zen_pcm::launch_to_float(c->in16 + b * ch, channels, m * hop, c->fin + b, c->s_in));
+		ZA_HIP(hipEventRecord(c->ev[k], c->s_in));
 		return ZEN_HIP_OK;
 	};
 	auto download = [&](size_t k, hipStream_t narrow_on, hipEvent_t after) -> int { // narrow piece k behind `after`, bring it down
 		size_t b, m;
 		span_of(k, &b, &m);
-		PF_HIP(hipStreamWaitEvent(narrow_on, after, 0));
+		ZA_HIP(hipStreamWaitEvent(narrow_on, after, 0));
 		for (int o = 0; o < 3; ++o)
 			if (hosts[o])
-				PF_HIP(zen_pcm::launch_from_float(c->fout[o] + b, m * hop, mode, gain, c->minmax + 2 * o, c->out16[o] + b, narrow_on));
+				ZA_HIP(zen_pcm::launch_from_float(c->fout[o] + b, m * hop, mode, gain, c->minmax + 2 * o, c->out16[o] + b, narrow_on));
 		if (narrow_on != c->s_out) {
-			PF_HIP(hipEventRecord(c->ev[2 * n_pieces + k], narrow_on));
-			PF_HIP(hipStreamWaitEvent(c->s_out, c->ev[2 * n_pieces + k], 0));
+			ZA_HIP(hipEventRecord(c->ev[2 * n_pieces + k], narrow_on));
+			ZA_HIP(hipStreamWaitEvent(c->s_out, c->ev[2 * n_pieces + k], 0));
 		}
 		for (int o = 0; o < 3; ++o)
 			if (hosts[o])
-				PF_HIP(hipMemcpyAsync(hosts[o] + b, c->out16[o] + b, 2 * m * hop, hipMemcpyDeviceToHost, c->s_out));
+				ZA_HIP(hipMemcpyAsync(hosts[o] + b, c->out16[o] + b, 2 * m * hop, hipMemcpyDeviceToHost, c->s_out));
 		return ZEN_HIP_OK;
 	};
 	bool tail_marked = false;
 	auto feed = [&]() -> int {
 		if (peak_mode)
-			PF_HIP(zen_pcm::launch_minmax_init(c->minmax, 3, c->run));
-		PF_TRY(upload(0));
+			ZA_HIP(zen_pcm::launch_minmax_init(c->minmax, 3, c->run));
+		ZA_TRY(upload(0));
 		for (size_t k = 0; k < n_pieces; ++k) {
 			size_t b, m;
 			span_of(k, &b, &m);
-			PF_HIP(hipStreamWaitEvent(c->run, c->ev[k], 0));
-			PF_ZEN(zen_hip_hpr_process(h, c->fin + b, m, m * hop, hosts[0] ? c->fout[0] + b : nullptr, hosts[1] ? c->fout[1] + b : nullptr,
+			ZA_HIP(hipStreamWaitEvent(c->run, c->ev[k], 0));
+			ZA_ZEN(zen_hip_hpr_process(h, c->fin + b, m, m * hop, hosts[0] ? c->fout[0] + b : nullptr, hosts[1] ? c->fout[1] + b : nullptr,
 			                           hosts[2] ? c->fout[2] + b : nullptr, m * hop));
 			if (peak_mode)
 				for (int o = 0; o < 3; ++o)
 					if (hosts[o])
-						PF_HIP(zen_pcm::launch_peak(c->fout[o] + b, m * hop, c->minmax + 2 * o, c->run));
-			PF_HIP(hipEventRecord(c->ev[n_pieces + k], c->run));
+						ZA_HIP(zen_pcm::launch_peak(c->fout[o] + b, m * hop, c->minmax + 2 * o, c->run));
+			ZA_HIP(hipEventRecord(c->ev[n_pieces + k], c->run));
 			// (copies from / to memory that could not be pinned block this thread: piece k+1 goes up before piece k comes down,
 			// so that the thread is never stuck behind kernels it has not fed yet)
 			if (k + 1 < n_pieces)
-				PF_TRY(upload(k + 1));
+				ZA_TRY(upload(k + 1));
 			if (!peak_mode)
-				PF_TRY(download(k, c->s_out, c->ev[n_pieces + k]));
+				ZA_TRY(download(k, c->s_out, c->ev[n_pieces + k]));
 		}
 		if (peak_mode) { // the peaks are known behind the last piece: narrow piece by piece on the engine's stream, each download under the next narrowing
-			PF_HIP(hipMemcpyAsync(c->minmax_host, c->minmax, 6 * sizeof(float), hipMemcpyDeviceToHost, c->run));
-			PF_HIP(hipEventRecord(c->ev[3 * n_pieces], c->run));
+			ZA_HIP(hipMemcpyAsync(c->minmax_host, c->minmax, 6 * sizeof(float), hipMemcpyDeviceToHost, c->run));
+			ZA_HIP(hipEventRecord(c->ev[3 * n_pieces], c->run));
 			tail_marked = true;
 			for (size_t k = 0; k < n_pieces; ++k)
-				PF_TRY(download(k, c->run, c->ev[n_pieces + n_pieces - 1]));
+				ZA_TRY(download(k, c->run, c->ev[n_pieces + n_pieces - 1]));
 		}
 		return ZEN_HIP_OK;
 	};
@@ -450,8 +412,8 @@ int zen_hip_pcm_hpr_process_host(zen_hip_hpr_t h, const int16_t* in_host, int ch
 		t_tail = now_ms();
 	// nothing may be in flight when the caller's buffers are unregistered and handed back
 	const int rc_sync = sync_all(c);
-	PF_TRY(rc);
-	PF_TRY(rc_sync);
+	ZA_TRY(rc);
+	ZA_TRY(rc_sync);
 	const double t_end = now_ms();
 	if (peak_mode && peaks)
 		for (int o = 0; o < 3; ++o)
@@ -466,33 +428,33 @@ int zen_hip_pcm_hpri_process(zen_hip_hpri_t h, const int16_t* audio_host, int ch
                              int16_t* resid, int mode, float gain, float peaks[3], size_t range_samples)
 {
 	if (!h)
-		PF_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpri_process: null handle");
-	PF_TRY(check_mode_channels("pcm_hpri_process", channels, mode));
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpri_process: null handle");
+	ZA_TRY(check_mode_channels("pcm_hpri_process", channels, mode));
 	const size_t n = n_frames, ch = (size_t)channels;
 	if (n == 0)
 		return ZEN_HIP_OK; // the reference returns three empty vectors
 	if (!audio_host)
-		PF_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpri_process: null argument");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpri_process: null argument");
 	int16_t* hosts[2] = {harm, perc};
 	{
 		const Span s[4] = {{(const char*)audio_host, 2 * ch * n}, {(const char*)harm, 2 * n}, {(const char*)perc, 2 * n}, {(const char*)resid, 2 * n}};
 		if (any_overlap(s, 4))
-			PF_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpri_process: the host buffers must not overlap");
+			ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpri_process: the host buffers must not overlap");
 	}
 	{ // refusals of the engine (clip too short, a handle of several clips) before anything is touched
 		size_t a, b;
-		PF_ZEN(zen_hip_hpri_range_halo(h, n, 0, n, &a, &b));
+		ZA_ZEN(zen_hip_hpri_range_halo(h, n, 0, n, &a, &b));
 	}
 	const double t_start = now_ms();
 	Ctx* c = nullptr;
-	PF_TRY(ctx_for(h, KIND_HPRI, &c));
-	PF_ZEN(zen_hip_hpri_set_stream(h, c->run));
-	PF_TRY(grow(c, c->in16, c->in16_cap, n * ch));
-	PF_TRY(grow(c, c->fin, c->fin_cap, n));
+	ZA_TRY(ctx_for(h, KIND_HPRI, &c));
+	ZA_ZEN(zen_hip_hpri_set_stream(h, c->run));
+	ZA_TRY(grow(c, c->in16, c->in16_cap, n * ch));
+	ZA_TRY(grow(c, c->fin, c->fin_cap, n));
 	for (int o = 0; o < 2; ++o)
 		if (hosts[o]) {
-			PF_TRY(grow(c, c->fout[o], c->fout_cap[o], n));
-			PF_TRY(grow(c, c->out16[o], c->out16_cap[o], n));
+			ZA_TRY(grow(c, c->fout[o], c->fout_cap[o], n));
+			ZA_TRY(grow(c, c->out16[o], c->out16_cap[o], n));
 		}
 	// ranges: the float path's rule (csrc/hpri.hip: shorter ranges cost more in warm-up halos and small grids than they hide in copies)
 	size_t want = range_samples;
@@ -504,7 +466,7 @@ int zen_hip_pcm_hpri_process(zen_hip_hpri_t h, const int16_t* audio_host, int ch
 	size_t n_ranges = ceil_div(n, want);
 	const size_t range = ceil_div(ceil_div(n, n_ranges), 16384) * 16384;
 	n_ranges = ceil_div(n, range);
-	PF_TRY(need_events(c, 3 * n_ranges + 1));
+	ZA_TRY(need_events(c, 3 * n_ranges + 1));
 	std::thread zero_thread;
 	if (resid) {
 		try {
@@ -541,59 +503,59 @@ int zen_hip_pcm_hpri_process(zen_hip_hpri_t h, const int16_t* audio_host, int ch
 	auto upload_to = [&](size_t k) -> int { // the frames range k reads, beyond what is up already
 		size_t b, e, in_b, in_e;
 		span_of(k, &b, &e);
-		PF_ZEN(zen_hip_hpri_range_halo(h, n, b, e, &in_b, &in_e));
+		ZA_ZEN(zen_hip_hpri_range_halo(h, n, b, e, &in_b, &in_e));
 		if (in_e > n)
 			in_e = n;
 		if (in_e > uploaded) {
-			PF_HIP(hipMemcpyAsync(c->in16 + uploaded * ch, audio_host + uploaded * ch, 2 * ch * (in_e - uploaded), hipMemcpyHostToDevice, c->s_in));
-			PF_HIP(zen_pcm::launch_to_float(c->in16 + uploaded * ch, channels, in_e - uploaded, c->fin + uploaded, c->s_in));
+			ZA_HIP(hipMemcpyAsync(c->in16 + uploaded * ch, audio_host + uploaded * ch, 2 * ch * (in_e - uploaded), hipMemcpyHostToDevice, c->s_in));
+			ZA_HIP(zen_pcm::launch_to_float(c->in16 + uploaded * ch, channels, in_e - uploaded, c->fin + uploaded, c->s_in));
 			uploaded = in_e;
 		}
-		PF_HIP(hipEventRecord(c->ev[k], c->s_in));
+		ZA_HIP(hipEventRecord(c->ev[k], c->s_in));
 		return ZEN_HIP_OK;
 	};
 	auto download = [&](size_t k, hipStream_t narrow_on, hipEvent_t after) -> int {
 		size_t b, e;
 		span_of(k, &b, &e);
-		PF_HIP(hipStreamWaitEvent(narrow_on, after, 0));
+		ZA_HIP(hipStreamWaitEvent(narrow_on, after, 0));
 		for (int o = 0; o < 2; ++o)
 			if (hosts[o])
-				PF_HIP(zen_pcm::launch_from_float(c->fout[o] + b, e - b, mode, gain, c->minmax + 2 * o, c->out16[o] + b, narrow_on));
+				ZA_HIP(zen_pcm::launch_from_float(c->fout[o] + b, e - b, mode, gain, c->minmax + 2 * o, c->out16[o] + b, narrow_on));
 		if (narrow_on != c->s_out) {
-			PF_HIP(hipEventRecord(c->ev[2 * n_ranges + k], narrow_on));
-			PF_HIP(hipStreamWaitEvent(c->s_out, c->ev[2 * n_ranges + k], 0));
+			ZA_HIP(hipEventRecord(c->ev[2 * n_ranges + k], narrow_on));
+			ZA_HIP(hipStreamWaitEvent(c->s_out, c->ev[2 * n_ranges + k], 0));
 		}
 		for (int o = 0; o < 2; ++o)
 			if (hosts[o])
-				PF_HIP(hipMemcpyAsync(hosts[o] + b, c->out16[o] + b, 2 * (e - b), hipMemcpyDeviceToHost, c->s_out));
+				ZA_HIP(hipMemcpyAsync(hosts[o] + b, c->out16[o] + b, 2 * (e - b), hipMemcpyDeviceToHost, c->s_out));
 		return ZEN_HIP_OK;
 	};
 	bool tail_marked = false;
 	auto feed = [&]() -> int {
 		if (peak_mode)
-			PF_HIP(zen_pcm::launch_minmax_init(c->minmax, 3, c->run));
-		PF_TRY(upload_to(0));
+			ZA_HIP(zen_pcm::launch_minmax_init(c->minmax, 3, c->run));
+		ZA_TRY(upload_to(0));
 		for (size_t k = 0; k < n_ranges; ++k) {
 			size_t b, e;
 			span_of(k, &b, &e);
-			PF_HIP(hipStreamWaitEvent(c->run, c->ev[k], 0));
-			PF_ZEN(zen_hip_hpri_process_range(h, c->fin, n, b, e, hosts[0] ? c->fout[0] + b : nullptr, hosts[1] ? c->fout[1] + b : nullptr));
+			ZA_HIP(hipStreamWaitEvent(c->run, c->ev[k], 0));
+			ZA_ZEN(zen_hip_hpri_process_range(h, c->fin, n, b, e, hosts[0] ? c->fout[0] + b : nullptr, hosts[1] ? c->fout[1] + b : nullptr));
 			if (peak_mode)
 				for (int o = 0; o < 2; ++o)
 					if (hosts[o])
-						PF_HIP(zen_pcm::launch_peak(c->fout[o] + b, e - b, c->minmax + 2 * o, c->run));
-			PF_HIP(hipEventRecord(c->ev[n_ranges + k], c->run));
+						ZA_HIP(zen_pcm::launch_peak(c->fout[o] + b, e - b, c->minmax + 2 * o, c->run));
+			ZA_HIP(hipEventRecord(c->ev[n_ranges + k], c->run));
 			if (k + 1 < n_ranges)
-				PF_TRY(upload_to(k + 1));
+				ZA_TRY(upload_to(k + 1));
 			if (!peak_mode)
-				PF_TRY(download(k, c->s_out, c->ev[n_ranges + k]));
+				ZA_TRY(download(k, c->s_out, c->ev[n_ranges + k]));
 		}
 		if (peak_mode) {
-			PF_HIP(hipMemcpyAsync(c->minmax_host, c->minmax, 6 * sizeof(float), hipMemcpyDeviceToHost, c->run));
-			PF_HIP(hipEventRecord(c->ev[3 * n_ranges], c->run));
+			ZA_HIP(hipMemcpyAsync(c->minmax_host, c->minmax, 6 * sizeof(float), hipMemcpyDeviceToHost, c->run));
+			ZA_HIP(hipEventRecord(c->ev[3 * n_ranges], c->run));
 			tail_marked = true;
 			for (size_t k = 0; k < n_ranges; ++k)
-				PF_TRY(download(k, c->run, c->ev[2 * n_ranges - 1]));
+				ZA_TRY(download(k, c->run, c->ev[2 * n_ranges - 1]));
 		}
 		return ZEN_HIP_OK;
 	};
@@ -602,8 +564,8 @@ int zen_hip_pcm_hpri_process(zen_hip_hpri_t h, const int16_t* audio_host, int ch
 	if (tail_marked && hipEventSynchronize(c->ev[3 * n_ranges]) == hipSuccess)
 		t_tail = now_ms();
 	const int rc_sync = sync_all(c);
-	PF_TRY(rc);
-	PF_TRY(rc_sync);
+	ZA_TRY(rc);
+	ZA_TRY(rc_sync);
 	const double t_end = now_ms();
 	if (peak_mode && peaks) {
 		for (int o = 0; o < 2; ++o)

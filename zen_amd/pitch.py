@@ -6,14 +6,11 @@ device.  No fallback: a missing library raises.
     with_hpr, without = pitch.track_hpr(x, 44100.0, 4096)  # the harmonic separation in front, all on the device
 """
 import ctypes as C
-import os
 
 import numpy as np
 
+from . import _addon
 from . import lib as _zl
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.environ.get("ZEN_HIP_PITCH_SO") or os.path.join(_HERE, "libzen_hip_pitch.so")
 
 KERNELS = ("pad", "fft_forward", "power", "fft_inverse", "pick")
 
@@ -38,32 +35,13 @@ SYMBOLS = [
     ("zen_hip_pitch_profile_get", _i, [_vp, _pd, _pull, _pull]),
 ]
 
-_lib = None
-
-
 def load():
-    """Load libzen_hip_pitch.so, building it first where it is absent (zen_amd/pitch_build.py; needs hipcc and a built
-    libzen_hip.so).  Raises if that fails."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO):
-            if "ZEN_HIP_PITCH_SO" in os.environ:
-                raise ImportError("%s does not exist" % _SO)
-            from . import pitch_build
-            pitch_build.build()
-        _zl.load()                      # the same libzen_hip.so for both bindings (found again beside this one by its rpath)
-        L = C.CDLL(_SO)
-        for name, res, args in SYMBOLS:
-            f = getattr(L, name)
-            f.restype = res
-            f.argtypes = args
-        _lib = L
-    return _lib
+    """Load libzen_hip_pitch.so, building it first where it is absent (_addon.load).  Raises if that fails."""
+    return _addon.load("pitch", SYMBOLS)
 
 
 def _ck(rc):
-    if rc:
-        raise _zl.ZenHipError(rc, load().zen_hip_pitch_last_error().decode())
+    _addon.check(rc, load().zen_hip_pitch_last_error)
 
 
 def _ptr(b):
@@ -124,10 +102,7 @@ class Pitch:
 
     def profile_get(self):
         """{"pad" | "fft_forward" | "power" | "fft_inverse" | "pick": {"ms", "bytes", "launches"}} since the last call; synchronises."""
-        k = len(KERNELS)
-        ms, by, n = (C.c_double * k)(), (C.c_ulonglong * k)(), (C.c_ulonglong * k)()
-        _ck(load().zen_hip_pitch_profile_get(self._h, ms, by, n))
-        return {name: {"ms": ms[i], "bytes": by[i], "launches": n[i]} for i, name in enumerate(KERNELS)}
+        return _addon.profile_get(_ck, load().zen_hip_pitch_profile_get, self._h, KERNELS)
 
 
 class HprTracker:

@@ -7,14 +7,11 @@ clips of UNEQUAL length.  No fallback: a missing library raises.
     groups, fraction = ragged.plan_groups([len(c) for c in clips], 16)   # a large library: sorted groups of 16 clips
 """
 import ctypes as C
-import os
 
 import numpy as np
 
+from . import _addon
 from . import lib as _zl
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.environ.get("ZEN_HIP_RAGGED_SO") or os.path.join(_HERE, "libzen_hip_ragged.so")
 
 KERNELS = ("pack", "splice", "trim")
 
@@ -37,35 +34,13 @@ SYMBOLS = [
     ("zen_hip_ragged_profile_get_engine", _i, [_vp, _i, _pd, _pull]),
 ]
 
-_lib = None
-
-
 def load():
-    """Load libzen_hip_ragged.so, building it first where it is absent (zen_amd/ragged_build.py; needs hipcc and a built
-    libzen_hip.so).  Raises if that fails."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO):
-            if "ZEN_HIP_RAGGED_SO" in os.environ:
-                raise ImportError("%s does not exist" % _SO)
-            from . import ragged_build
-            ragged_build.build()
-        _zl.load()                      # the same libzen_hip.so for both bindings (found again beside this one by its rpath)
-        L = C.CDLL(_SO)
-        for name, res, args in SYMBOLS:
-            f = getattr(L, name)
-            f.restype = res
-            f.argtypes = args
-        _lib = L
-    return _lib
+    """Load libzen_hip_ragged.so, building it first where it is absent (_addon.load).  Raises if that fails."""
+    return _addon.load("ragged", SYMBOLS)
 
 
 def _ck(rc):
-    if rc:
-        msg = load().zen_hip_ragged_last_error().decode()
-        if rc == _zl.E_HOPS_NOT_DIVISIBLE:
-            raise _zl.ZgException(rc, msg)
-        raise _zl.ZenHipError(rc, msg)
+    _addon.check(rc, load().zen_hip_ragged_last_error, (_zl.E_HOPS_NOT_DIVISIBLE,))
 
 
 def _lens(lens, n_clips):
@@ -127,19 +102,11 @@ class Ragged:
 
     def profile_get(self):
         """{"pack" | "splice" | "trim": {"ms", "bytes", "launches"}} since the last call; synchronises."""
-        ms, by, n = (C.c_double * 3)(), (C.c_ulonglong * 3)(), (C.c_ulonglong * 3)()
-        _ck(load().zen_hip_ragged_profile_get(self._h, ms, by, n))
-        return {k: {"ms": ms[i], "bytes": by[i], "launches": n[i]} for i, k in enumerate(KERNELS)}
+        return _addon.profile_get(_ck, load().zen_hip_ragged_profile_get, self._h, KERNELS)
 
     def profile_get_engine(self):
         """The engines' per-class kernel times, as HPRIOffline.profile_get_all."""
-        names = ("stft", "freq_filter", "time_filter", "istft", "finalize", "rt_fused")
-        out = {}
-        for ps in (1, 2):
-            ms, n = (C.c_double * 6)(), (C.c_ulonglong * 6)()
-            _ck(load().zen_hip_ragged_profile_get_engine(self._h, ps, ms, n))
-            out["pass%d" % ps] = {k: {"ms": ms[i], "launches": n[i]} for i, k in enumerate(names)}
-        return out
+        return _addon.profile_get_engine(_ck, load().zen_hip_ragged_profile_get_engine, self._h)
 
 
 def plan_groups(lengths, group):

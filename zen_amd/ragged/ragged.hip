@@ -7,58 +7,15 @@
 // up) the intermediates exist in memory here: H1, P1, R1 and P2 are written by the engines and read back by splice / trim.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <vector>
-
 #include "zen_hip_ragged.h"
 
+#include "../addon/hpri_pair.h"
 #include "ragged_kernels.h"
 
+using namespace zen_addon;
 using zen_ragged::tab_t;
 
 namespace {
-
-thread_local char t_err[512] = "";
-
-void set_err(const char* fmt, ...)
-{
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(t_err, sizeof(t_err), fmt, ap);
-	va_end(ap);
-}
-
-#define RG_FAIL(code, ...)    \
-	do {                      \
-		set_err(__VA_ARGS__); \
-		return (code);        \
-	} while (0)
-#define RG_HIP(call)                                                                            \
-	do {                                                                                        \
-		hipError_t e__ = (call);                                                                \
-		if (e__ != hipSuccess) {                                                                \
-			set_err("%s:%d: %s failed: %s", __FILE__, __LINE__, #call, hipGetErrorString(e__)); \
-			return ZEN_HIP_E_HIP;                                                               \
-		}                                                                                       \
-	} while (0)
-// a call into libzen_hip.so: its message becomes ours
-#define RG_ZEN(call)                                        \
-	do {                                                    \
-		int rc__ = (call);                                  \
-		if (rc__ != ZEN_HIP_OK) {                           \
-			set_err("%s: %s", #call, zen_hip_last_error()); \
-			return rc__;                                    \
-		}                                                   \
-	} while (0)
-#define RG_TRY(expr)            \
-	do {                        \
-		int rc__ = (expr);      \
-		if (rc__ != ZEN_HIP_OK) \
-			return rc__;        \
-	} while (0)
 
 constexpr int TAB_SLOTS = 4;
 enum { K_PACK = 0, K_SPLICE = 1, K_TRIM = 2 };
@@ -72,47 +29,30 @@ struct TabSlot {
 	bool in_flight = false;
 };
 
-struct Timed {
-	int kernel;
-	hipEvent_t e0, e1;
-};
-
 } // namespace
 
-struct zen_hip_ragged {
-	zen_hip_hpr_t e1 = nullptr; // hop_h; H, P, R; anticausal (csrc/hpri.hip:85-87)
-	zen_hip_hpr_t e2 = nullptr; // hop_p; P only; anticausal (csrc/hpri.hip:89-90)
-	size_t hop_h = 0, hop_p = 0, n_clips = 0, lag_h = 0, lag_p = 0;
+struct zen_hip_ragged : HpriPair {
+	size_t hop_h = 0, hop_p = 0, n_clips = 0;
 	hipStream_t stream = nullptr;
 	// scratch, grown on demand: the zero-padded input rows, pass 1's outputs, pass 2's input and output
 	float *staged = nullptr, *h1 = nullptr, *p1 = nullptr, *r1 = nullptr, *in2 = nullptr, *p2 = nullptr;
 	size_t staged_cap = 0, h1_cap = 0, p1_cap = 0, r1_cap = 0, in2_cap = 0, p2_cap = 0; // floats
 	TabSlot tab[TAB_SLOTS];
 	unsigned next_slot = 0;
-	bool profile = false;
-	std::vector<Timed> timed;
-	double prof_ms[3] = {0, 0, 0};
-	unsigned long long prof_bytes[3] = {0, 0, 0}, prof_launches[3] = {0, 0, 0};
+	Profiler<3> prof;
 };
 
 namespace {
-
-// hps.cu:109-126 hpss_chunk_padder: float ceil of a float quotient, plus `lag` chunks
-size_t chunk_padder(size_t audio_size, size_t hop, size_t lag)
-{
-	const int n = (int)(ceilf((float)audio_size / (float)hop)) + (int)lag;
-	return n > 0 ? (size_t)n * hop : 0;
-}
 
 int grow(zen_hip_ragged* h, float*& p, size_t& cap, size_t want)
 {
 	if (want <= cap)
 		return ZEN_HIP_OK;
-	RG_HIP(hipStreamSynchronize(h->stream)); // queued calls may still use the buffer
+	ZA_HIP(hipStreamSynchronize(h->stream)); // queued calls may still use the buffer
 	(void)zen_hip_free(p);
 	p = nullptr; // a failed allocation below must not leave a freed pointer behind a stale capacity
 	cap = 0;
-	RG_ZEN(zen_hip_malloc((void**)&p, sizeof(float) * want));
+	ZA_ZEN(zen_hip_malloc((void**)&p, sizeof(float) * want));
 	cap = want;
 	return ZEN_HIP_OK;
 }
@@ -135,12 +75,12 @@ int make_plan(zen_hip_ragged* h, const size_t* lens, Plan* pl)
 		return ZEN_HIP_OK;
 	TabSlot& t = h->tab[h->next_slot++ % TAB_SLOTS];
 	if (!t.host) {
-		RG_ZEN(zen_hip_host_alloc_mapped(sizeof(tab_t) * 2 * C, 0, (void**)&t.host, (void**)&t.host_dev));
-		RG_ZEN(zen_hip_malloc((void**)&t.dev, sizeof(tab_t) * 2 * C));
-		RG_HIP(hipEventCreateWithFlags(&t.copied, hipEventDisableTiming));
+		ZA_ZEN(zen_hip_host_alloc_mapped(sizeof(tab_t) * 2 * C, 0, (void**)&t.host, (void**)&t.host_dev));
+		ZA_ZEN(zen_hip_malloc((void**)&t.dev, sizeof(tab_t) * 2 * C));
+		ZA_HIP(hipEventCreateWithFlags(&t.copied, hipEventDisableTiming));
 	}
 	if (t.in_flight)
-		RG_HIP(hipEventSynchronize(t.copied));
+		ZA_HIP(hipEventSynchronize(t.copied));
 	t.in_flight = false;
 	for (size_t c = 0; c < C; ++c) {
 		const size_t n = lens[c];
@@ -153,42 +93,17 @@ int make_plan(zen_hip_ragged* h, const size_t* lens, Plan* pl)
 			pl->row2 = pad2;
 	}
 	if (pl->row1 == 0 || pl->row2 == 0)
-		RG_FAIL(ZEN_HIP_E_BAD_ARG, "ragged: clip lengths out of range");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "ragged: clip lengths out of range");
 	for (size_t c = 0; c < C; ++c) {
 		pl->sum_len += t.host[c];
 		pl->sum_q += t.host[C + c] < pl->row2 ? t.host[C + c] : pl->row2;
 	}
-	RG_HIP(hipMemcpyAsync(t.dev, t.host, sizeof(tab_t) * 2 * C, hipMemcpyHostToDevice, h->stream));
-	RG_HIP(hipEventRecord(t.copied, h->stream));
+	ZA_HIP(hipMemcpyAsync(t.dev, t.host, sizeof(tab_t) * 2 * C, hipMemcpyHostToDevice, h->stream));
+	ZA_HIP(hipEventRecord(t.copied, h->stream));
 	t.in_flight = true;
 	pl->tab_dev = t.dev;
 	return ZEN_HIP_OK;
 }
-
-struct KernelTimer { // HIP events around one launch of this library's kernels while profiling is on
-	zen_hip_ragged* h;
-	Timed t = {0, nullptr, nullptr};
-	int begin(int kernel, unsigned long long bytes)
-	{
-		if (!h->profile)
-			return ZEN_HIP_OK;
-		t.kernel = kernel;
-		RG_HIP(hipEventCreate(&t.e0));
-		RG_HIP(hipEventCreate(&t.e1));
-		RG_HIP(hipEventRecord(t.e0, h->stream));
-		h->prof_bytes[kernel] += bytes;
-		h->prof_launches[kernel] += 1;
-		return ZEN_HIP_OK;
-	}
-	int end()
-	{
-		if (!h->profile)
-			return ZEN_HIP_OK;
-		RG_HIP(hipEventRecord(t.e1, h->stream));
-		h->timed.push_back(t);
-		return ZEN_HIP_OK;
-	}
-};
 
 // Steps 1, 3, 4, 5 (and 6 where perc_dev is given) of a call, on rows that are already in h->staged.
 // harm_dev / perc_dev: the caller's result rows or NULL; want_h1 / want_p2: H1 / P2 are wanted in scratch all the same (the
@@ -200,45 +115,38 @@ int run_passes(zen_hip_ragged* h, const Plan& pl, float* harm_dev, float* perc_d
 	if (!harm && !perc)
 		return ZEN_HIP_OK;
 	if (harm)
-		RG_TRY(grow(h, h->h1, h->h1_cap, C * pl.row1));
+		ZA_TRY(grow(h, h->h1, h->h1_cap, C * pl.row1));
 	if (perc) {
-		RG_TRY(grow(h, h->p1, h->p1_cap, C * pl.row1));
-		RG_TRY(grow(h, h->r1, h->r1_cap, C * pl.row1));
-		RG_TRY(grow(h, h->in2, h->in2_cap, C * pl.row2));
-		RG_TRY(grow(h, h->p2, h->p2_cap, C * pl.row2));
+		ZA_TRY(grow(h, h->p1, h->p1_cap, C * pl.row1));
+		ZA_TRY(grow(h, h->r1, h->r1_cap, C * pl.row1));
+		ZA_TRY(grow(h, h->in2, h->in2_cap, C * pl.row2));
+		ZA_TRY(grow(h, h->p2, h->p2_cap, C * pl.row2));
 	}
 	// pass 1: large hop over the longest clip's hop count (hps.cu:142-167)
-	RG_ZEN(zen_hip_hpr_process(h->e1, h->staged, pl.row1 / h->hop_h, pl.row1, harm ? h->h1 : nullptr, perc ? h->p1 : nullptr,
+	ZA_ZEN(zen_hip_hpr_process(h->e1, h->staged, pl.row1 / h->hop_h, pl.row1, harm ? h->h1 : nullptr, perc ? h->p1 : nullptr,
 	                           perc ? h->r1 : nullptr, pl.row1));
 	if (perc || harm_dev) {
-		KernelTimer kt{h};
+		auto kt = h->prof.on_stream(h->stream);
 		unsigned long long bytes = 0;
 		if (perc)
 			bytes += sizeof(float) * (2 * pl.sum_q + C * pl.row2);
 		if (harm_dev)
 			bytes += sizeof(float) * (pl.sum_len + C * pl.max_len);
-		RG_TRY(kt.begin(K_SPLICE, bytes));
-		RG_HIP(zen_ragged::launch_splice(h->h1, h->p1, h->r1, pl.row1, sh1, pl.tab_dev, C, perc ? h->in2 : nullptr, pl.row2, harm_dev,
+		ZA_TRY(kt.begin(K_SPLICE, bytes));
+		ZA_HIP(zen_ragged::launch_splice(h->h1, h->p1, h->r1, pl.row1, sh1, pl.tab_dev, C, perc ? h->in2 : nullptr, pl.row2, harm_dev,
 		                                 out_stride, pl.max_len, h->stream));
-		RG_TRY(kt.end());
+		ZA_TRY(kt.end());
 	}
 	if (!perc)
 		return ZEN_HIP_OK;
 	// pass 2: small hop on the spliced sum, percussive only (hps.cu:185-205)
-	RG_ZEN(zen_hip_hpr_process(h->e2, h->in2, pl.row2 / h->hop_p, pl.row2, nullptr, h->p2, nullptr, pl.row2));
+	ZA_ZEN(zen_hip_hpr_process(h->e2, h->in2, pl.row2 / h->hop_p, pl.row2, nullptr, h->p2, nullptr, pl.row2));
 	if (perc_dev) {
-		KernelTimer kt{h};
-		RG_TRY(kt.begin(K_TRIM, sizeof(float) * (pl.sum_len + C * pl.max_len)));
-		RG_HIP(zen_ragged::launch_trim(h->p2, pl.row2, sh2, pl.tab_dev, C, perc_dev, out_stride, pl.max_len, h->stream));
-		RG_TRY(kt.end());
+		auto kt = h->prof.on_stream(h->stream);
+		ZA_TRY(kt.begin(K_TRIM, sizeof(float) * (pl.sum_len + C * pl.max_len)));
+		ZA_HIP(zen_ragged::launch_trim(h->p2, pl.row2, sh2, pl.tab_dev, C, perc_dev, out_stride, pl.max_len, h->stream));
+		ZA_TRY(kt.end());
 	}
-	return ZEN_HIP_OK;
-}
-
-int reset_engines(zen_hip_ragged* h) // each call is a fresh pair of HPR objects' state
-{
-	RG_ZEN(zen_hip_hpr_reset_buffers(h->e1));
-	RG_ZEN(zen_hip_hpr_reset_buffers(h->e2));
 	return ZEN_HIP_OK;
 }
 
@@ -253,31 +161,20 @@ int zen_hip_ragged_create(float fs, size_t hop_h, size_t hop_p, float beta_h, fl
                           zen_hip_ragged_t* h)
 {
 	if (!h || n_clips == 0)
-		RG_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_create: null handle or zero clips");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_create: null handle or zero clips");
 	if (hop_p == 0 || hop_h % hop_p != 0) // hps.cu:33-36
-		RG_FAIL(ZEN_HIP_E_HOPS_NOT_DIVISIBLE, "hop_h and hop_p should be evenly divisible");
+		ZA_FAIL(ZEN_HIP_E_HOPS_NOT_DIVISIBLE, "hop_h and hop_p should be evenly divisible");
 	zen_hip_ragged* o = new zen_hip_ragged;
 	o->hop_h = hop_h;
 	o->hop_p = hop_p;
 	o->n_clips = n_clips;
-	int rc = zen_hip_hpr_create(fs, hop_h, beta_h, ZEN_HIP_OUTPUT_HARMONIC | ZEN_HIP_OUTPUT_PERCUSSIVE | ZEN_HIP_OUTPUT_RESIDUAL,
-	                            ZEN_HIP_TIME_ANTICAUSAL, !nocopybord, n_clips, 0, &o->e1);
-	if (rc == ZEN_HIP_OK)
-		rc = zen_hip_hpr_create(fs, hop_p, beta_p, ZEN_HIP_OUTPUT_PERCUSSIVE, ZEN_HIP_TIME_ANTICAUSAL, !nocopybord, n_clips, 0, &o->e2);
-	zen_hip_hpr_params p1, p2;
-	if (rc == ZEN_HIP_OK)
-		rc = zen_hip_hpr_get_params(o->e1, &p1);
-	if (rc == ZEN_HIP_OK)
-		rc = zen_hip_hpr_get_params(o->e2, &p2);
+	const int rc = pair_create(o, fs, hop_h, hop_p, beta_h, beta_p, nocopybord, n_clips);
 	if (rc != ZEN_HIP_OK) {
 		set_err("ragged_create: %s", zen_hip_last_error());
-		zen_hip_hpr_destroy(o->e1);
-		zen_hip_hpr_destroy(o->e2);
+		pair_destroy(o);
 		delete o;
 		return rc;
 	}
-	o->lag_h = (size_t)p1.lag;
-	o->lag_p = (size_t)p2.lag;
 	*h = o;
 	return ZEN_HIP_OK;
 }
@@ -287,8 +184,7 @@ int zen_hip_ragged_destroy(zen_hip_ragged_t h)
 	if (!h)
 		return ZEN_HIP_OK;
 	(void)hipStreamSynchronize(h->stream);
-	zen_hip_hpr_destroy(h->e1);
-	zen_hip_hpr_destroy(h->e2);
+	pair_destroy(h);
 	float* bufs[6] = {h->staged, h->h1, h->p1, h->r1, h->in2, h->p2};
 	for (float* b : bufs)
 		(void)zen_hip_free(b);
@@ -299,10 +195,7 @@ int zen_hip_ragged_destroy(zen_hip_ragged_t h)
 		if (t.copied)
 			(void)hipEventDestroy(t.copied);
 	}
-	for (Timed& t : h->timed) {
-		(void)hipEventDestroy(t.e0);
-		(void)hipEventDestroy(t.e1);
-	}
+	h->prof.release();
 	delete h;
 	return ZEN_HIP_OK;
 }
@@ -310,10 +203,9 @@ int zen_hip_ragged_destroy(zen_hip_ragged_t h)
 int zen_hip_ragged_set_stream(zen_hip_ragged_t h, void* stream)
 {
 	if (!h)
-		RG_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_set_stream: null handle");
-	RG_ZEN(zen_hip_hpr_set_stream(h->e1, stream)); // (each waits for what the previous stream holds)
-	RG_ZEN(zen_hip_hpr_set_stream(h->e2, stream));
-	RG_HIP(hipStreamSynchronize(h->stream));
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_set_stream: null handle");
+	ZA_TRY(pair_set_stream(h, stream));
+	ZA_HIP(hipStreamSynchronize(h->stream));
 	h->stream = (hipStream_t)stream;
 	return ZEN_HIP_OK;
 }
@@ -321,25 +213,21 @@ int zen_hip_ragged_set_stream(zen_hip_ragged_t h, void* stream)
 int zen_hip_ragged_use_sse_filter(zen_hip_ragged_t h)
 {
 	if (!h)
-		RG_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
-	RG_ZEN(zen_hip_hpr_use_sse_filter(h->e1));
-	RG_ZEN(zen_hip_hpr_use_sse_filter(h->e2));
-	return ZEN_HIP_OK;
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
+	return pair_use_sse_filter(h);
 }
 
 int zen_hip_ragged_use_soft_mask(zen_hip_ragged_t h)
 {
 	if (!h)
-		RG_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
-	RG_ZEN(zen_hip_hpr_use_soft_mask(h->e1));
-	RG_ZEN(zen_hip_hpr_use_soft_mask(h->e2));
-	return ZEN_HIP_OK;
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
+	return pair_use_soft_mask(h);
 }
 
 int zen_hip_ragged_hop_counts(zen_hip_ragged_t h, size_t max_len, size_t* n_hops_h, size_t* n_hops_p)
 {
 	if (!h)
-		RG_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
 	if (n_hops_h)
 		*n_hops_h = max_len ? chunk_padder(max_len, h->hop_h, h->lag_h) / h->hop_h : 0;
 	if (n_hops_p)
@@ -351,27 +239,27 @@ int zen_hip_ragged_process_device(zen_hip_ragged_t h, const float* audio_dev, co
                                   float* perc_dev, size_t out_stride)
 {
 	if (!h || !audio_dev || !lens)
-		RG_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_process_device: null argument");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_process_device: null argument");
 	if (((uintptr_t)audio_dev & 3) || ((uintptr_t)harm_dev & 3) || ((uintptr_t)perc_dev & 3))
-		RG_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_process_device: float pointers need 4-byte alignment");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_process_device: float pointers need 4-byte alignment");
 	size_t max_len = 0;
 	for (size_t c = 0; c < h->n_clips; ++c)
 		if (lens[c] > max_len)
 			max_len = lens[c];
 	if (stride < max_len || out_stride < max_len)
-		RG_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_process_device: stride %zu / out_stride %zu below the longest clip (%zu samples)", stride,
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_process_device: stride %zu / out_stride %zu below the longest clip (%zu samples)", stride,
 		        out_stride, max_len);
 	if (max_len == 0 || (!harm_dev && !perc_dev))
 		return ZEN_HIP_OK; // empty clips: nothing to write
 	Plan pl;
-	RG_TRY(make_plan(h, lens, &pl));
-	RG_TRY(grow(h, h->staged, h->staged_cap, h->n_clips * pl.row1));
-	RG_TRY(reset_engines(h));
+	ZA_TRY(make_plan(h, lens, &pl));
+	ZA_TRY(grow(h, h->staged, h->staged_cap, h->n_clips * pl.row1));
+	ZA_TRY(pair_reset_buffers(h)); // each call is a fresh pair of HPR objects' state
 	{
-		KernelTimer kt{h};
-		RG_TRY(kt.begin(K_PACK, sizeof(float) * (pl.sum_len + h->n_clips * pl.row1)));
-		RG_HIP(zen_ragged::launch_pack(audio_dev, stride, pl.tab_dev, h->n_clips, h->staged, pl.row1, h->stream));
-		RG_TRY(kt.end());
+		auto kt = h->prof.on_stream(h->stream);
+		ZA_TRY(kt.begin(K_PACK, sizeof(float) * (pl.sum_len + h->n_clips * pl.row1)));
+		ZA_HIP(zen_ragged::launch_pack(audio_dev, stride, pl.tab_dev, h->n_clips, h->staged, pl.row1, h->stream));
+		ZA_TRY(kt.end());
 	}
 	return run_passes(h, pl, harm_dev, perc_dev, out_stride, false, false);
 }
@@ -380,28 +268,28 @@ int zen_hip_ragged_process_host(zen_hip_ragged_t h, const float* const* clips, c
                                 float* const* perc)
 {
 	if (!h || !clips || !lens)
-		RG_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_process_host: null argument");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_process_host: null argument");
 	const size_t C = h->n_clips;
 	bool want_h = false, want_p = false;
 	for (size_t c = 0; c < C; ++c) {
 		if (lens[c] && !clips[c])
-			RG_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_process_host: clip %zu is null", c);
+			ZA_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_process_host: clip %zu is null", c);
 		want_h = want_h || (harm && harm[c] && lens[c]);
 		want_p = want_p || (perc && perc[c] && lens[c]);
 	}
 	if (!want_h && !want_p)
 		return ZEN_HIP_OK;
 	Plan pl;
-	RG_TRY(make_plan(h, lens, &pl));
-	RG_TRY(grow(h, h->staged, h->staged_cap, C * pl.row1));
-	RG_TRY(reset_engines(h));
+	ZA_TRY(make_plan(h, lens, &pl));
+	ZA_TRY(grow(h, h->staged, h->staged_cap, C * pl.row1));
+	ZA_TRY(pair_reset_buffers(h)); // each call is a fresh pair of HPR objects' state
 	// every clip straight into its row, zeros behind it: no padded matrix on the host, no pack launch
 	for (size_t c = 0; c < C; ++c) {
 		float* row = h->staged + c * pl.row1;
 		if (lens[c])
-			RG_HIP(hipMemcpyAsync(row, clips[c], sizeof(float) * lens[c], hipMemcpyHostToDevice, h->stream));
+			ZA_HIP(hipMemcpyAsync(row, clips[c], sizeof(float) * lens[c], hipMemcpyHostToDevice, h->stream));
 		if (lens[c] < pl.row1)
-			RG_HIP(hipMemsetAsync(row + lens[c], 0, sizeof(float) * (pl.row1 - lens[c]), h->stream));
+			ZA_HIP(hipMemsetAsync(row + lens[c], 0, sizeof(float) * (pl.row1 - lens[c]), h->stream));
 	}
 	int rc = run_passes(h, pl, nullptr, nullptr, 0, want_h, want_p);
 	// the results come down from where the engines wrote them: harm_c = H1_c[sh1 ..], perc_c = P2_c[sh2 ..], lens[c] samples
@@ -416,55 +304,33 @@ int zen_hip_ragged_process_host(zen_hip_ragged_t h, const float* const* clips, c
 			e = hipMemcpyAsync(perc[c], h->p2 + c * pl.row2 + sh2, sizeof(float) * lens[c], hipMemcpyDeviceToHost, h->stream);
 	}
 	const hipError_t es = hipStreamSynchronize(h->stream); // whatever happened, nothing of this call stays in flight
-	RG_TRY(rc);
-	RG_HIP(e);
-	RG_HIP(es);
+	ZA_TRY(rc);
+	ZA_HIP(e);
+	ZA_HIP(es);
 	return ZEN_HIP_OK;
 }
 
 int zen_hip_ragged_profile(zen_hip_ragged_t h, int enable)
 {
 	if (!h)
-		RG_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
-	RG_ZEN(zen_hip_hpr_profile(h->e1, enable));
-	RG_ZEN(zen_hip_hpr_profile(h->e2, enable));
-	h->profile = enable != 0;
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
+	ZA_TRY(pair_profile(h, enable));
+	h->prof.on = enable != 0;
 	return ZEN_HIP_OK;
 }
 
 int zen_hip_ragged_profile_get(zen_hip_ragged_t h, double ms[3], unsigned long long bytes[3], unsigned long long launches[3])
 {
 	if (!h || !ms || !bytes || !launches)
-		RG_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_profile_get: null argument");
-	hipError_t e = hipSuccess;
-	for (Timed& t : h->timed) {
-		float v = 0.f;
-		if (e == hipSuccess)
-			e = hipEventSynchronize(t.e1);
-		if (e == hipSuccess)
-			e = hipEventElapsedTime(&v, t.e0, t.e1);
-		h->prof_ms[t.kernel] += v;
-		(void)hipEventDestroy(t.e0);
-		(void)hipEventDestroy(t.e1);
-	}
-	h->timed.clear();
-	for (int k = 0; k < 3; ++k) {
-		ms[k] = h->prof_ms[k];
-		bytes[k] = h->prof_bytes[k];
-		launches[k] = h->prof_launches[k];
-		h->prof_ms[k] = 0;
-		h->prof_bytes[k] = h->prof_launches[k] = 0;
-	}
-	RG_HIP(e);
-	return ZEN_HIP_OK;
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_profile_get: null argument");
+	return h->prof.drain(ms, bytes, launches);
 }
 
 int zen_hip_ragged_profile_get_engine(zen_hip_ragged_t h, int pass, double ms[6], unsigned long long launches[6])
 {
 	if (!h || (pass != 1 && pass != 2))
-		RG_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_profile_get_engine: pass must be 1 or 2");
-	RG_ZEN(zen_hip_hpr_profile_get_all(pass == 1 ? h->e1 : h->e2, ms, launches));
-	return ZEN_HIP_OK;
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_profile_get_engine: pass must be 1 or 2");
+	return pair_profile_get_engine(h, pass, ms, launches);
 }
 
 } // extern "C"

@@ -2,14 +2,11 @@
 // zero-padded rows), splice (pass 1's outputs into pass 2's input rows and the harmonic result rows) and trim (pass 2's
 // output into the percussive result rows).
 //
-// Shape of all three: blockIdx.y walks the clips, the workgroups of a clip walk its destination row in a grid-stride loop
-// over groups of 4 floats that start on a 16-byte boundary OF THE DESTINATION (global_store_dwordx4), with a scalar head in
-// front of the first boundary and a scalar tail behind the last whole group: the caller's pointers and strides only promise
-// 4-byte alignment.  A group's source is read with one global_load_dwordx4 where its address happens to be 16-byte aligned
-// too (always, between the buffers of this library: their rows are multiples of the hop and so are the shifts), with four
-// dword loads otherwise.  A group that straddles one of the row's boundaries (the clip's end, the splice points) is
-// assembled sample by sample, so nothing beyond a clip's own samples is ever read.  No LDS, no atomics.  The grid is capped
-// at 8 workgroups of 256 threads per CU (32 wavefronts, the most a CU holds).
+// Shape of all three: blockIdx.y walks the clips, the workgroups of a clip walk its destination row as ../addon/row_walk.h
+// describes (16-byte stores on the destination's boundaries, a scalar head and tail).  A group's source is 16-byte aligned
+// between the buffers of this library: their rows are multiples of the hop and so are the shifts.  A group that straddles
+// one of the row's boundaries (the clip's end, the splice points) is assembled sample by sample, so nothing beyond a clip's
+// own samples is ever read.
 //
 // The only arithmetic is Q = P1 + R1: one IEEE binary32 add, what the engine's `add` destination and the reference's
 // sum_vectors_functor (libzen/hps.h:142-150) compute.
@@ -19,39 +16,14 @@
 
 #include "ragged_kernels.h"
 
+#include "../addon/row_walk.h"
+
 #pragma clang fp contract(off)
 
 namespace zen_ragged {
 namespace {
 
-constexpr int TPB = 256;
-
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-__device__ __forceinline__ float4 load4(const float* __restrict__ p)
-{
-	if (aligned16(p))
-		return *reinterpret_cast<const float4*>(p);
-	return make_float4(p[0], p[1], p[2], p[3]);
-}
-
-// The walk over one destination row of `len` floats: one(j) gives sample j, four(j0) the samples j0 .. j0+3 (all < len).
-template <class One, class Four>
-__device__ __forceinline__ void walk_row(float* __restrict__ dst, size_t len, size_t tid, size_t nthreads, One one, Four four)
-{
-	size_t head = ((16 - ((uintptr_t)dst & 15)) & 15) / 4; // floats in front of the first 16-byte boundary of dst
-	if (head > len)
-		head = len;
-	const size_t n_groups = (len - head) / 4, tail = head + n_groups * 4;
-	for (size_t j = tid; j < head; j += nthreads)
-		dst[j] = one(j);
-	for (size_t j = tail + tid; j < len; j += nthreads)
-		dst[j] = one(j);
-	for (size_t g = tid; g < n_groups; g += nthreads) {
-		const size_t j0 = head + g * 4;
-		*reinterpret_cast<float4*>(dst + j0) = four(j0);
-	}
-}
+using namespace zen_addon;
 
 // dst[j] = j < n ? src[j] : 0 for j < len (n <= len); src[n] and beyond is not read
 __device__ __forceinline__ void copy_zero_tail(float* __restrict__ dst, const float* __restrict__ src, size_t n, size_t len,
@@ -120,27 +92,6 @@ __global__ __launch_bounds__(TPB) void splice_kernel(const float* __restrict__ h
 		if (harm)
 			copy_zero_tail(harm + c * out_stride, h1 + c * row1 + sh1, n, max_len, tid, nthreads);
 	}
-}
-
-// gx workgroups per clip x gy clips: enough to cover a row of `len` floats, at most 8 workgroups per CU over the grid
-dim3 grid_for(size_t len, size_t n_clips)
-{
-	static unsigned cap = 0;
-	if (!cap) {
-		int dev = 0, cus = 0;
-		if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-			cus = 256;
-		(void)hipGetLastError();
-		cap = 8u * (unsigned)cus;
-	}
-	const unsigned gy = (unsigned)(n_clips < 65535 ? n_clips : 65535);
-	size_t gx = ((len + 3) / 4 + TPB - 1) / TPB;
-	const size_t gx_cap = cap / gy > 0 ? cap / gy : 1;
-	if (gx > gx_cap)
-		gx = gx_cap;
-	if (gx < 1)
-		gx = 1;
-	return dim3((unsigned)gx, gy, 1);
 }
 
 } // namespace
