@@ -325,6 +325,30 @@ def test_realtime_block_against_the_oracle(pcm, oracle, cli_encode, name, pieces
         pcm.release(g)
 
 
+@pytest.mark.parametrize("piece_hops, n_pieces", ((1, 9), (1000, 1)), ids=("every_piece_one_hop", "piece_longer_than_the_block"))
+def test_realtime_piece_size_edges(pcm, oracle, piece_hops, n_pieces):
+    """the two ends of the piece rule on a block of 9 hops: as many pieces as hops, and a piece clamped to the block; both
+    give the model's samples, so the same samples as each other"""
+    cfg = dict(RT_CONFIGS["hop256_all"], n_hops=9)
+    g, x16, ch, ref, wanted = rt_case(oracle, cfg, seed=3)
+    try:
+        outs, peaks = run_pcm(pcm, g, x16, ch, wanted, mode=pcm.PEAK, piece_hops=piece_hops)
+        st = pcm.host_stats()
+        assert st["n_pieces"] == n_pieces and st["piece_frames"] == 9 * 256 // n_pieces
+        for i, (k, nm) in enumerate(KEYS):
+            pk = M.peak_of(ref[k])
+            assert peaks[i].tobytes() == pk.tobytes(), (k, peaks[i], pk)
+            assert np.array_equal(outs[nm], M.from_float_peak(ref[k], pk)), k
+        g.reset_buffers()
+        outs, none = run_pcm(pcm, g, x16, ch, wanted, mode=pcm.GAIN, gain=1.5, piece_hops=piece_hops)
+        st = pcm.host_stats()
+        assert none is None and st["n_pieces"] == n_pieces and st["piece_frames"] == 9 * 256 // n_pieces
+        for k, nm in wanted:
+            assert np.array_equal(outs[nm], M.from_float_gain(ref[k], 1.5)), k
+    finally:
+        pcm.release(g)
+
+
 def test_realtime_two_calls_equal_one_call_and_float_path(pcm, oracle):
     import zen_amd
     cfg = RT_CONFIGS["hop256_all"]
@@ -525,6 +549,29 @@ def test_offline_clip_of_several_ranges(pcm, oracle, soft):
         assert np.array_equal(pin_out.array, hh)
         pin_in.free()
         pin_out.free()
+    finally:
+        pcm.release(g)
+
+
+def test_offline_ranges_shorter_than_their_halo(pcm, oracle):
+    """ranges of 16384 samples at hops 4096 / 256, whose look-ahead is longer than a range: the input is all up before the
+    last range is reached, and a range that has nothing to add still records that its input is up"""
+    range_samples = 16384
+    n = 6 * range_samples + 5003
+    g, x16, rh, rp = offline_case(oracle, n, 70, hops=(4096, 256))
+    hh, pp, rr = (np.full(n, 12345, np.int16) for _ in range(3))
+    try:
+        n_ranges = -(-n // range_samples)
+        in_end = [min(n, g.range_halo(n, k * range_samples, min(n, (k + 1) * range_samples))[1]) for k in range(n_ranges)]
+        # the test's own premise
+        assert any(in_end[k] <= in_end[k - 1] for k in range(1, n_ranges)), in_end
+        assert any(in_end[k] >= n for k in range(n_ranges - 1)), in_end
+        pk = pcm.hpri_process(g, x16, harm=hh, perc=pp, resid=rr, mode=pcm.PEAK, range_samples=range_samples)
+        st = pcm.host_stats()
+        assert st["n_pieces"] == n_ranges == 7 and st["piece_frames"] == range_samples
+        assert pk.tobytes() == np.array([M.peak_of(rh), M.peak_of(rp), 0], np.float32).tobytes()
+        assert np.array_equal(hh, M.from_float_peak(rh, pk[0])) and np.array_equal(pp, M.from_float_peak(rp, pk[1]))
+        assert not rr.any()
     finally:
         pcm.release(g)
 

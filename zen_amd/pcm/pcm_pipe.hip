@@ -1,10 +1,11 @@
 // pcm_pipe.hip -- the C ABI of libzen_hip_pcm.so (zen_hip_pcm.h): the three kernels on device pointers, and the two
-// host-to-host pipelines that put them between 2-byte copies and the float engines of libzen_hip.so.
+// host-to-host calls that put them between 2-byte copies and the float engines of libzen_hip.so.
 //
-// The pipelines are the three-stream pattern of zen_hip_hpr_process_host / zen_hip_hpri_process (csrc/hpr.hip, csrc/hpri.hip)
-// written a second time on top of the engines' public C ABI: piece k+1 goes up and is widened on the upload stream, piece k
-// runs on the engine's stream, piece k-1 is narrowed and comes down on the download stream.  The engines' sources are not
-// touched by this; folding the two pipelines together inside the engine is left to a change that can carry a fuzz run.
+// One pipeline, two callers.  run_pieces is the three-stream pattern of zen_hip_hpr_process_host / zen_hip_hpri_process
+// (csrc/hpr.hip, csrc/hpri.hip) on top of the engines' public C ABI: piece k+1 goes up and is widened on the upload stream,
+// piece k runs on the engine's stream, piece k-1 is narrowed and comes down on the download stream.  The two entry points
+// check their arguments, size the pieces and supply what their engine differs in.  The engines' sources are not touched by
+// this; folding this pipeline into theirs is left to a change that can carry a fuzz run.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -198,6 +199,135 @@ int check_mode_channels(const char* who, int channels, int mode)
 	return ZEN_HIP_OK;
 }
 
+// ---- the piece pipeline ----------------------------------------------------------------------------------------------------
+struct Job {
+	const int16_t* in_host;
+	int channels, mode;
+	size_t n, piece;   // samples of the call and of a piece (the last piece may be shorter)
+	int16_t* hosts[3]; // harmonic, percussive, residual; NULL: not wanted, or not the pipeline's to write (HPRIOffline's residual)
+	float gain, *peaks; // peaks: NULL, or where PEAK mode writes the three peaks
+};
+
+// Runs the job piece by piece: piece k+1 goes up and is widened on s_in, piece k runs on the engine's stream, piece k-1 is
+// narrowed and comes down on s_out.  What the engines differ in comes as three calls into libzen_hip.so, each returning its
+// code: bind(stream) puts the engine on the context's stream, in_end(b, e, &end) says how far the input must be up before
+// piece [b, e) runs, engine(fin, b, e, out) runs it (fin: sample 0 of the call; out[o]: where sample b goes, or NULL).
+template <class Bind, class InEnd, class Engine>
+int run_pieces(void* h, int kind, const Job& j, Bind bind, InEnd in_end, Engine engine)
+{
+	const double t_start = now_ms();
+	const size_t n = j.n, ch = (size_t)j.channels, n_pieces = ceil_div(n, j.piece);
+	int16_t* const* hosts = j.hosts;
+	const bool peak_mode = j.mode == ZEN_HIP_PCM_PEAK;
+	Ctx* c = nullptr;
+	ZA_TRY(ctx_for(h, kind, &c));
+	ZA_ZEN_AS(bind(c->run), "the engine's set_stream");
+	ZA_TRY(grow(c, c->in16, c->in16_cap, n * ch));
+	ZA_TRY(grow(c, c->fin, c->fin_cap, n));
+	for (int o = 0; o < 3; ++o)
+		if (hosts[o]) {
+			ZA_TRY(grow(c, c->fout[o], c->fout_cap[o], n));
+			ZA_TRY(grow(c, c->out16[o], c->out16_cap[o], n));
+		}
+	// events: [k] piece k is up and widened, [n_pieces + k] piece k is through the engine (PEAK: and folded into min / max),
+	// [2 n_pieces + k] PEAK: piece k is narrowed, [3 n_pieces] PEAK: the peaks are known
+	ZA_TRY(need_events(c, 3 * n_pieces + 1));
+	Registered reg_in, reg_out[3];
+	reg_in.take(j.in_host, 2 * ch * n, true);
+	for (int o = 0; o < 3; ++o)
+		reg_out[o].take(hosts[o], 2 * n, true);
+	memset(&t_stats, 0, sizeof(t_stats));
+	t_stats.n_pieces = n_pieces;
+	t_stats.piece_frames = j.piece;
+	t_stats.input_pinned = reg_in.pinned;
+	t_stats.outputs_pinned = (!hosts[0] || reg_out[0].pinned) && (!hosts[1] || reg_out[1].pinned) && (!hosts[2] || reg_out[2].pinned);
+	t_stats.setup_ms = now_ms() - t_start;
+	auto span_of = [&](size_t k, size_t* b, size_t* e) {
+		*b = k * j.piece;
+		*e = *b + j.piece < n ? *b + j.piece : n;
+	};
+	size_t uploaded = 0;
+	auto upload = [&](size_t k) -> int { // the samples piece k reads, beyond what is up already
+		size_t b, e, end;
+		span_of(k, &b, &e);
+		ZA_ZEN_AS(in_end(b, e, &end), "the engine's range_halo");
+		if (end > n)
+			end = n;
+		if (end > uploaded) {
+			ZA_HIP(hipMemcpyAsync(c->in16 + uploaded * ch, j.in_host + uploaded * ch, 2 * ch * (end - uploaded), hipMemcpyHostToDevice, c->s_in));
+			ZA_HIP(zen_pcm::launch_to_float(c->in16 + uploaded * ch, j.channels, end - uploaded, c->fin + uploaded, c->s_in));
+			uploaded = end;
+		}
+		ZA_HIP(hipEventRecord(c->ev[k], c->s_in));
+		return ZEN_HIP_OK;
+	};
+	auto download = [&](size_t k, hipStream_t narrow_on, hipEvent_t after) -> int { // narrow piece k behind `after`, bring it down
+		size_t b, e;
+		span_of(k, &b, &e);
+		ZA_HIP(hipStreamWaitEvent(narrow_on, after, 0));
+		for (int o = 0; o < 3; ++o)
+			if (hosts[o])
+				ZA_HIP(zen_pcm::launch_from_float(c->fout[o] + b, e - b, j.mode, j.gain, c->minmax + 2 * o, c->out16[o] + b, narrow_on));
+		if (narrow_on != c->s_out) {
+			ZA_HIP(hipEventRecord(c->ev[2 * n_pieces + k], narrow_on));
+			ZA_HIP(hipStreamWaitEvent(c->s_out, c->ev[2 * n_pieces + k], 0));
+		}
+		for (int o = 0; o < 3; ++o)
+			if (hosts[o])
+				ZA_HIP(hipMemcpyAsync(hosts[o] + b, c->out16[o] + b, 2 * (e - b), hipMemcpyDeviceToHost, c->s_out));
+		return ZEN_HIP_OK;
+	};
+	bool tail_marked = false;
+	auto feed = [&]() -> int {
+		if (peak_mode)
+			ZA_HIP(zen_pcm::launch_minmax_init(c->minmax, 3, c->run));
+		ZA_TRY(upload(0));
+		for (size_t k = 0; k < n_pieces; ++k) {
+			size_t b, e;
+			span_of(k, &b, &e);
+			float* out[3];
+			for (int o = 0; o < 3; ++o)
+				out[o] = hosts[o] ? c->fout[o] + b : nullptr;
+			ZA_HIP(hipStreamWaitEvent(c->run, c->ev[k], 0));
+			ZA_ZEN_AS(engine(c->fin, b, e, out), "the engine's process call");
+			if (peak_mode)
+				for (int o = 0; o < 3; ++o)
+					if (hosts[o])
+						ZA_HIP(zen_pcm::launch_peak(out[o], e - b, c->minmax + 2 * o, c->run));
+			ZA_HIP(hipEventRecord(c->ev[n_pieces + k], c->run));
+			// (copies from / to memory that could not be pinned block this thread: piece k+1 goes up before piece k comes down,
+			// so that the thread is never stuck behind kernels it has not fed yet)
+			if (k + 1 < n_pieces)
+				ZA_TRY(upload(k + 1));
+			if (!peak_mode)
+				ZA_TRY(download(k, c->s_out, c->ev[n_pieces + k]));
+		}
+		if (peak_mode) { // the peaks are known behind the last piece: narrow piece by piece on the engine's stream, each download under the next narrowing
+			ZA_HIP(hipMemcpyAsync(c->minmax_host, c->minmax, 6 * sizeof(float), hipMemcpyDeviceToHost, c->run));
+			ZA_HIP(hipEventRecord(c->ev[3 * n_pieces], c->run));
+			tail_marked = true;
+			for (size_t k = 0; k < n_pieces; ++k)
+				ZA_TRY(download(k, c->run, c->ev[2 * n_pieces - 1]));
+		}
+		return ZEN_HIP_OK;
+	};
+	const int rc = feed();
+	double t_tail = 0;
+	if (tail_marked && hipEventSynchronize(c->ev[3 * n_pieces]) == hipSuccess)
+		t_tail = now_ms();
+	// nothing may be in flight when the caller's buffers are unregistered and handed back
+	const int rc_sync = sync_all(c);
+	ZA_TRY(rc);
+	ZA_TRY(rc_sync);
+	const double t_end = now_ms();
+	if (peak_mode && j.peaks)
+		for (int o = 0; o < 3; ++o)
+			j.peaks[o] = hosts[o] ? pcm16_peak_of(c->minmax_host[2 * o], c->minmax_host[2 * o + 1]) : 0.f;
+	t_stats.tail_ms = t_tail > 0 ? t_end - t_tail : 0;
+	t_stats.total_ms = t_end - t_start;
+	return ZEN_HIP_OK;
+}
+
 } // namespace
 
 static_assert(ZEN_HIP_PCM_PEAK == ZEN_PCM_MODE_PEAK && ZEN_HIP_PCM_GAIN == ZEN_PCM_MODE_GAIN, "public and kernel-side mode values agree");
@@ -290,7 +420,7 @@ int zen_hip_pcm_release_all(void)
 	return ZEN_HIP_OK;
 }
 
-// ---- realtime block engine -------------------------------------------------------------------------------------------------
+// ---- realtime block engine: pieces of hops, three outputs ------------------------------------------------------------------
 int zen_hip_pcm_hpr_process_host(zen_hip_hpr_t h, const int16_t* in_host, int channels, size_t n_hops, int16_t* harm, int16_t* perc,
                                  int16_t* resid, int mode, float gain, float peaks[3], size_t piece_hops)
 {
@@ -304,126 +434,25 @@ int zen_hip_pcm_hpr_process_host(zen_hip_hpr_t h, const int16_t* in_host, int ch
 	if (n_hops == 0)
 		return ZEN_HIP_OK;
 	const size_t hop = P.hop, n = n_hops * hop, ch = (size_t)channels;
-	int16_t* hosts[3] = {harm, perc, resid};
 	{
 		const Span s[4] = {{(const char*)in_host, 2 * ch * n}, {(const char*)harm, 2 * n}, {(const char*)perc, 2 * n}, {(const char*)resid, 2 * n}};
 		if (any_overlap(s, 4))
 			ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpr_process_host: the host buffers must not overlap (pieces come down while later pieces go up)");
 	}
-	const double t_start = now_ms();
-	Ctx* c = nullptr;
-	ZA_TRY(ctx_for(h, KIND_HPR, &c));
-	ZA_ZEN(zen_hip_hpr_set_stream(h, c->run));
-	ZA_TRY(grow(c, c->in16, c->in16_cap, n * ch));
-	ZA_TRY(grow(c, c->fin, c->fin_cap, n));
-	for (int o = 0; o < 3; ++o)
-		if (hosts[o]) {
-			ZA_TRY(grow(c, c->fout[o], c->fout_cap[o], n));
-			ZA_TRY(grow(c, c->out16[o], c->out16_cap[o], n));
-		}
 	// default pieces: 4 Mi samples in GAIN mode -- 8 MiB on the link per piece and direction, the float path's rule in bytes --
 	// and 8 Mi in PEAK mode, where nothing comes down inside the loop and the pieces only pace the uploads and the tail
 	// (measured on the headline block, profiles/pcm16_piece_sweep.jsonl: GAIN 2.48 / 1.86 / 1.60 / 1.54 / 1.66 / 2.00 ms and
 	// PEAK 4.22 / 3.32 / 2.84 / 2.49 / 2.39 / 2.37 ms at 0.5 / 1 / 2 / 4 / 8 / 12.6 Mi samples per piece)
-	const bool peak_mode = mode == ZEN_HIP_PCM_PEAK;
-	size_t piece = piece_hops ? piece_hops : ((size_t)(peak_mode ? 8 : 4) << 20) / hop;
-	if (piece < 1)
-		piece = 1;
-	if (piece > n_hops)
-		piece = n_hops;
-	const size_t n_pieces = ceil_div(n_hops, piece);
-	// events: [k] piece k is up and widened, [n_pieces + k] piece k is through the engine (PEAK: and folded into min / max),
-	// [2 n_pieces + k] PEAK: piece k is narrowed, [3 n_pieces] PEAK: the peaks are known
-	ZA_TRY(need_events(c, 3 * n_pieces + 1));
-	Registered reg_in, reg_out[3];
-	reg_in.take(in_host, 2 * ch * n, true);
-	for (int o = 0; o < 3; ++o)
-		reg_out[o].take(hosts[o], 2 * n, true);
-	memset(&t_stats, 0, sizeof(t_stats));
-	t_stats.n_pieces = n_pieces;
-	t_stats.piece_frames = piece * hop;
-	t_stats.input_pinned = reg_in.pinned;
-	t_stats.outputs_pinned = (!hosts[0] || reg_out[0].pinned) && (!hosts[1] || reg_out[1].pinned) && (!hosts[2] || reg_out[2].pinned);
-	t_stats.setup_ms = now_ms() - t_start;
-	auto span_of = [&](size_t k, size_t* b, size_t* m) { // piece k: first sample, hops
-		const size_t h0 = k * piece;
-		*m = h0 + piece < n_hops ? piece : n_hops - h0;
-		*b = h0 * hop;
-	};
-	auto upload = [&](size_t k) -> int {
-		size_t b, m;
-		span_of(k, &b, &m);
-		ZA_HIP(hipMemcpyAsync(c->in16 + b * ch, in_host + b * ch, 2 * ch * m * hop, hipMemcpyHostToDevice, c->s_in));
-		ZA_HIP(zen_pcm::launch_to_float(c->in16 + b * ch, channels, m * hop, c->fin + b, c->s_in));
-		ZA_HIP(hipEventRecord(c->ev[k], c->s_in));
-		return ZEN_HIP_OK;
-	};
-	auto download = [&](size_t k, hipStream_t narrow_on, hipEvent_t after) -> int { // narrow piece k behind `after`, bring it down
-		size_t b, m;
-		span_of(k, &b, &m);
-		ZA_HIP(hipStreamWaitEvent(narrow_on, after, 0));
-		for (int o = 0; o < 3; ++o)
-			if (hosts[o])
-				ZA_HIP(zen_pcm::launch_from_float(c->fout[o] + b, m * hop, mode, gain, c->minmax + 2 * o, c->out16[o] + b, narrow_on));
-		if (narrow_on != c->s_out) {
-			ZA_HIP(hipEventRecord(c->ev[2 * n_pieces + k], narrow_on));
-			ZA_HIP(hipStreamWaitEvent(c->s_out, c->ev[2 * n_pieces + k], 0));
-		}
-		for (int o = 0; o < 3; ++o)
-			if (hosts[o])
-				ZA_HIP(hipMemcpyAsync(hosts[o] + b, c->out16[o] + b, 2 * m * hop, hipMemcpyDeviceToHost, c->s_out));
-		return ZEN_HIP_OK;
-	};
-	bool tail_marked = false;
-	auto feed = [&]() -> int {
-		if (peak_mode)
-			ZA_HIP(zen_pcm::launch_minmax_init(c->minmax, 3, c->run));
-		ZA_TRY(upload(0));
-		for (size_t k = 0; k < n_pieces; ++k) {
-			size_t b, m;
-			span_of(k, &b, &m);
-			ZA_HIP(hipStreamWaitEvent(c->run, c->ev[k], 0));
-			ZA_ZEN(zen_hip_hpr_process(h, c->fin + b, m, m * hop, hosts[0] ? c->fout[0] + b : nullptr, hosts[1] ? c->fout[1] + b : nullptr,
-			                           hosts[2] ? c->fout[2] + b : nullptr, m * hop));
-			if (peak_mode)
-				for (int o = 0; o < 3; ++o)
-					if (hosts[o])
-						ZA_HIP(zen_pcm::launch_peak(c->fout[o] + b, m * hop, c->minmax + 2 * o, c->run));
-			ZA_HIP(hipEventRecord(c->ev[n_pieces + k], c->run));
-			// (copies from / to memory that could not be pinned block this thread: piece k+1 goes up before piece k comes down,
-			// so that the thread is never stuck behind kernels it has not fed yet)
-			if (k + 1 < n_pieces)
-				ZA_TRY(upload(k + 1));
-			if (!peak_mode)
-				ZA_TRY(download(k, c->s_out, c->ev[n_pieces + k]));
-		}
-		if (peak_mode) { // the peaks are known behind the last piece: narrow piece by piece on the engine's stream, each download under the next narrowing
-			ZA_HIP(hipMemcpyAsync(c->minmax_host, c->minmax, 6 * sizeof(float), hipMemcpyDeviceToHost, c->run));
-			ZA_HIP(hipEventRecord(c->ev[3 * n_pieces], c->run));
-			tail_marked = true;
-			for (size_t k = 0; k < n_pieces; ++k)
-				ZA_TRY(download(k, c->run, c->ev[n_pieces + n_pieces - 1]));
-		}
-		return ZEN_HIP_OK;
-	};
-	const int rc = feed();
-	double t_tail = 0;
-	if (tail_marked && hipEventSynchronize(c->ev[3 * n_pieces]) == hipSuccess)
-		t_tail = now_ms();
-	// nothing may be in flight when the caller's buffers are unregistered and handed back
-	const int rc_sync = sync_all(c);
-	ZA_TRY(rc);
-	ZA_TRY(rc_sync);
-	const double t_end = now_ms();
-	if (peak_mode && peaks)
-		for (int o = 0; o < 3; ++o)
-			peaks[o] = hosts[o] ? pcm16_peak_of(c->minmax_host[2 * o], c->minmax_host[2 * o + 1]) : 0.f;
-	t_stats.tail_ms = t_tail > 0 ? t_end - t_tail : 0;
-	t_stats.total_ms = t_end - t_start;
-	return ZEN_HIP_OK;
+	size_t piece = piece_hops ? piece_hops : ((size_t)(mode == ZEN_HIP_PCM_PEAK ? 8 : 4) << 20) / hop;
+	piece = piece < 1 ? 1 : piece > n_hops ? n_hops : piece;
+	const Job job = {in_host, channels, mode, n, piece * hop, {harm, perc, resid}, gain, peaks};
+	return run_pieces(
+	    h, KIND_HPR, job, [&](hipStream_t run) { return zen_hip_hpr_set_stream(h, run); },
+	    [](size_t, size_t e, size_t* end) { return *end = e, ZEN_HIP_OK; }, // a block reads no further than it writes
+	    [&](const float* fin, size_t b, size_t e, float* const out[3]) { return zen_hip_hpr_process(h, fin + b, (e - b) / hop, e - b, out[0], out[1], out[2], e - b); });
 }
 
-// ---- offline two-pass engine -----------------------------------------------------------------------------------------------
+// ---- offline two-pass engine: ranges of samples with their halos, two outputs and a zeroed residual -----------------------
 int zen_hip_pcm_hpri_process(zen_hip_hpri_t h, const int16_t* audio_host, int channels, size_t n_frames, int16_t* harm, int16_t* perc,
                              int16_t* resid, int mode, float gain, float peaks[3], size_t range_samples)
 {
@@ -435,38 +464,20 @@ int zen_hip_pcm_hpri_process(zen_hip_hpri_t h, const int16_t* audio_host, int ch
 		return ZEN_HIP_OK; // the reference returns three empty vectors
 	if (!audio_host)
 		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpri_process: null argument");
-	int16_t* hosts[2] = {harm, perc};
 	{
 		const Span s[4] = {{(const char*)audio_host, 2 * ch * n}, {(const char*)harm, 2 * n}, {(const char*)perc, 2 * n}, {(const char*)resid, 2 * n}};
 		if (any_overlap(s, 4))
 			ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpri_process: the host buffers must not overlap");
 	}
-	{ // refusals of the engine (clip too short, a handle of several clips) before anything is touched
-		size_t a, b;
-		ZA_ZEN(zen_hip_hpri_range_halo(h, n, 0, n, &a, &b));
-	}
-	const double t_start = now_ms();
-	Ctx* c = nullptr;
-	ZA_TRY(ctx_for(h, KIND_HPRI, &c));
-	ZA_ZEN(zen_hip_hpri_set_stream(h, c->run));
-	ZA_TRY(grow(c, c->in16, c->in16_cap, n * ch));
-	ZA_TRY(grow(c, c->fin, c->fin_cap, n));
-	for (int o = 0; o < 2; ++o)
-		if (hosts[o]) {
-			ZA_TRY(grow(c, c->fout[o], c->fout_cap[o], n));
-			ZA_TRY(grow(c, c->out16[o], c->out16_cap[o], n));
-		}
+	size_t a, b; // refusals of the engine (clip too short, a handle of several clips) before anything is touched
+	ZA_ZEN(zen_hip_hpri_range_halo(h, n, 0, n, &a, &b));
 	// ranges: the float path's rule (csrc/hpri.hip: shorter ranges cost more in warm-up halos and small grids than they hide in copies)
 	size_t want = range_samples;
-	if (want == 0) {
-		want = n >= ((size_t)1 << 25) ? (size_t)1 << 23 : (size_t)1 << 22;
-		if (n < ((size_t)1 << 23))
-			want = n;
-	}
-	size_t n_ranges = ceil_div(n, want);
-	const size_t range = ceil_div(ceil_div(n, n_ranges), 16384) * 16384;
-	n_ranges = ceil_div(n, range);
-	ZA_TRY(need_events(c, 3 * n_ranges + 1));
+	if (want == 0) // 8 Mi samples from 32 Mi up, 4 Mi below, the whole clip below 8 Mi
+		want = n >= ((size_t)1 << 25) ? (size_t)1 << 23 : n < ((size_t)1 << 23) ? n : (size_t)1 << 22;
+	const size_t range = ceil_div(ceil_div(n, ceil_div(n, want)), 16384) * 16384;
+	// the never-written residual: zeros, beside the pipeline.  Declared before the call that registers the caller's buffers, so
+	// that on every path out they are unregistered (behind sync_all) first and the thread is joined last
 	std::thread zero_thread;
 	if (resid) {
 		try {
@@ -484,97 +495,11 @@ int zen_hip_pcm_hpri_process(zen_hip_hpri_t h, const int16_t* audio_host, int ch
 				t.join();
 		}
 	} joiner{zero_thread};
-	Registered reg_in, reg_out[2];
-	reg_in.take(audio_host, 2 * ch * n, true);
-	for (int o = 0; o < 2; ++o)
-		reg_out[o].take(hosts[o], 2 * n, true);
-	memset(&t_stats, 0, sizeof(t_stats));
-	t_stats.n_pieces = n_ranges;
-	t_stats.piece_frames = range;
-	t_stats.input_pinned = reg_in.pinned;
-	t_stats.outputs_pinned = (!hosts[0] || reg_out[0].pinned) && (!hosts[1] || reg_out[1].pinned);
-	t_stats.setup_ms = now_ms() - t_start;
-	const bool peak_mode = mode == ZEN_HIP_PCM_PEAK;
-	auto span_of = [&](size_t k, size_t* b, size_t* e) {
-		*b = k * range;
-		*e = *b + range < n ? *b + range : n;
-	};
-	size_t uploaded = 0;
-	auto upload_to = [&](size_t k) -> int { // the frames range k reads, beyond what is up already
-		size_t b, e, in_b, in_e;
-		span_of(k, &b, &e);
-		ZA_ZEN(zen_hip_hpri_range_halo(h, n, b, e, &in_b, &in_e));
-		if (in_e > n)
-			in_e = n;
-		if (in_e > uploaded) {
-			ZA_HIP(hipMemcpyAsync(c->in16 + uploaded * ch, audio_host + uploaded * ch, 2 * ch * (in_e - uploaded), hipMemcpyHostToDevice, c->s_in));
-			ZA_HIP(zen_pcm::launch_to_float(c->in16 + uploaded * ch, channels, in_e - uploaded, c->fin + uploaded, c->s_in));
-			uploaded = in_e;
-		}
-		ZA_HIP(hipEventRecord(c->ev[k], c->s_in));
-		return ZEN_HIP_OK;
-	};
-	auto download = [&](size_t k, hipStream_t narrow_on, hipEvent_t after) -> int {
-		size_t b, e;
-		span_of(k, &b, &e);
-		ZA_HIP(hipStreamWaitEvent(narrow_on, after, 0));
-		for (int o = 0; o < 2; ++o)
-			if (hosts[o])
-				ZA_HIP(zen_pcm::launch_from_float(c->fout[o] + b, e - b, mode, gain, c->minmax + 2 * o, c->out16[o] + b, narrow_on));
-		if (narrow_on != c->s_out) {
-			ZA_HIP(hipEventRecord(c->ev[2 * n_ranges + k], narrow_on));
-			ZA_HIP(hipStreamWaitEvent(c->s_out, c->ev[2 * n_ranges + k], 0));
-		}
-		for (int o = 0; o < 2; ++o)
-			if (hosts[o])
-				ZA_HIP(hipMemcpyAsync(hosts[o] + b, c->out16[o] + b, 2 * (e - b), hipMemcpyDeviceToHost, c->s_out));
-		return ZEN_HIP_OK;
-	};
-	bool tail_marked = false;
-	auto feed = [&]() -> int {
-		if (peak_mode)
-			ZA_HIP(zen_pcm::launch_minmax_init(c->minmax, 3, c->run));
-		ZA_TRY(upload_to(0));
-		for (size_t k = 0; k < n_ranges; ++k) {
-			size_t b, e;
-			span_of(k, &b, &e);
-			ZA_HIP(hipStreamWaitEvent(c->run, c->ev[k], 0));
-			ZA_ZEN(zen_hip_hpri_process_range(h, c->fin, n, b, e, hosts[0] ? c->fout[0] + b : nullptr, hosts[1] ? c->fout[1] + b : nullptr));
-			if (peak_mode)
-				for (int o = 0; o < 2; ++o)
-					if (hosts[o])
-						ZA_HIP(zen_pcm::launch_peak(c->fout[o] + b, e - b, c->minmax + 2 * o, c->run));
-			ZA_HIP(hipEventRecord(c->ev[n_ranges + k], c->run));
-			if (k + 1 < n_ranges)
-				ZA_TRY(upload_to(k + 1));
-			if (!peak_mode)
-				ZA_TRY(download(k, c->s_out, c->ev[n_ranges + k]));
-		}
-		if (peak_mode) {
-			ZA_HIP(hipMemcpyAsync(c->minmax_host, c->minmax, 6 * sizeof(float), hipMemcpyDeviceToHost, c->run));
-			ZA_HIP(hipEventRecord(c->ev[3 * n_ranges], c->run));
-			tail_marked = true;
-			for (size_t k = 0; k < n_ranges; ++k)
-				ZA_TRY(download(k, c->run, c->ev[2 * n_ranges - 1]));
-		}
-		return ZEN_HIP_OK;
-	};
-	const int rc = feed();
-	double t_tail = 0;
-	if (tail_marked && hipEventSynchronize(c->ev[3 * n_ranges]) == hipSuccess)
-		t_tail = now_ms();
-	const int rc_sync = sync_all(c);
-	ZA_TRY(rc);
-	ZA_TRY(rc_sync);
-	const double t_end = now_ms();
-	if (peak_mode && peaks) {
-		for (int o = 0; o < 2; ++o)
-			peaks[o] = hosts[o] ? pcm16_peak_of(c->minmax_host[2 * o], c->minmax_host[2 * o + 1]) : 0.f;
-		peaks[2] = 0.f;
-	}
-	t_stats.tail_ms = t_tail > 0 ? t_end - t_tail : 0;
-	t_stats.total_ms = t_end - t_start;
-	return ZEN_HIP_OK;
+	const Job job = {audio_host, channels, mode, n, range, {harm, perc, nullptr}, gain, peaks};
+	return run_pieces(
+	    h, KIND_HPRI, job, [&](hipStream_t run) { return zen_hip_hpri_set_stream(h, run); },
+	    [&](size_t b, size_t e, size_t* end) { return zen_hip_hpri_range_halo(h, n, b, e, &b, end); }, // a range reads its halo
+	    [&](const float* fin, size_t b, size_t e, float* const out[3]) { return zen_hip_hpri_process_range(h, fin, n, b, e, out[0], out[1]); });
 }
 
 } // extern "C"
