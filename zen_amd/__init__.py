@@ -8,7 +8,7 @@ library is missing or no GPU is present the calls raise.
 from .lib import (  # noqa: F401
     FREQUENCY, OUTPUT_HARMONIC, OUTPUT_PERCUSSIVE, OUTPUT_RESIDUAL, TIME_ANTICAUSAL, TIME_CAUSAL,
     BoxFilterGPU, DeviceBuffer, Event, FFTC2CWrapperGPU, HPR, HPRIOffline, HPRRealtime, IOGPU, MedianFilterGPU, PinnedHost,
-    ZenHipError, ZgException, debug_poke, device_name, init, load, memcheck, run_plan, set_option, synchronize,
+    ZenHipError, ZgException, blockrun_set, blockrun_stats, debug_poke, device_name, init, load, memcheck, run_plan, set_option, synchronize,
 )
 # the add-on builders under the names their four modules had: `from zen_amd import pcm_build` keeps working
 from .addon_build import live as live_build, pcm as pcm_build, pitch as pitch_build, ragged as ragged_build  # noqa: F401,E402

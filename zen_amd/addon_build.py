@@ -1,5 +1,5 @@
 """Builds the add-on libraries for gfx950 with hipcc: zen_amd/libzen_hip_<name>.so from zen_amd/<name>/, each a library of
-its own on top of libzen_hip.so's C ABI, and the demo program zen_amd/bin/pitch-track (plain g++: it reaches the GPU through
+its own on top of libzen_hip.so's C ABI (blockrun: on top of the engine's state as well), and the demo program zen_amd/bin/pitch-track (plain g++: it reaches the GPU through
 the two C ABIs only).
 
     python zen_amd/addon_build.py [name ...] [--force]         # no name: all of them
@@ -27,12 +27,13 @@ class Addon:
     """One add-on: zen_amd/<name>/<sources> -> zen_amd/build_<name>/*.o -> zen_amd/libzen_hip_<name>.so.  `extra_deps`: files
     outside its directory whose change makes its objects stale; `build_demo`: a step behind the link."""
 
-    def __init__(self, name, sources, extra_deps=(), build_demo=None, title=None):
+    def __init__(self, name, sources, extra_deps=(), build_demo=None, title=None, file_flags=None):
         self.name, self.SOURCES, self.build_demo, self.title = name, list(sources), build_demo, title or name
         self.SRC = os.path.join(HERE, name)
         self.OUT = os.path.join(HERE, "libzen_hip_%s.so" % name)
         self.OBJDIR = os.path.join(HERE, "build_" + name)
         self.FLAGS = FLAGS
+        self.FILE_FLAGS = dict(file_flags or {})   # source -> flags of its own behind FLAGS (as build.py's FILE_FLAGS)
         self.extra_deps = [os.path.join(HERE, *d.split("/")) for d in extra_deps]
 
     def deps(self):
@@ -51,7 +52,7 @@ class Addon:
         newest = max(os.path.getmtime(p) for p in [srcp] + self.deps())
         if os.path.exists(obj) and os.path.getmtime(obj) >= newest:
             return obj, False
-        subprocess.check_call([HIPCC] + self.FLAGS + ["-c", srcp, "-o", obj])
+        subprocess.check_call([HIPCC] + self.FLAGS + self.FILE_FLAGS.get(src, []) + ["-c", srcp, "-o", obj])
         return obj, True
 
     def build(self, force=False, verbose=False):
@@ -95,10 +96,22 @@ pcm = Addon("pcm", ["pcm_kernels.hip", "pcm_pipe.hip"], extra_deps=["csrc/host_p
 ragged = Addon("ragged", ["ragged_kernels.hip", "ragged.hip"])
 live = Addon("live", ["live_kernels.hip", "live.hip"])
 pitch = Addon("pitch", ["pitch_kernels.hip", "pitch.hip"], build_demo=build_demo)
-ADDONS = {a.name: a for a in (pcm, ragged, live, pitch)}
+ADDONS = {a.name: a for a in (pcm, ragged, live, pitch)}   # on the C ABI alone
+# blockrun shares the engine's state with libzen_hip.so at compile time (csrc/hpr_engine.h) and compiles the fused kernel's
+# headers into a kernel of its own: the csrc headers it includes make its objects stale, and its kernel file gets the
+# scheduler flags build.py gives rt_fused.hip, plus fft_dev.h's LDS-only barrier between the passes of a transform (a run
+# keeps loads and stores in flight across them) and its folded image addresses (with them the run kernel fits its 168
+# registers without scratch; without, it spills 5).
+blockrun = Addon("blockrun", ["blockrun_kernel.hip", "blockrun.hip"],
+                 extra_deps=["csrc/hpr_engine.h", "csrc/rt_fused.h", "csrc/common.h", "csrc/bounds.h", "csrc/memguard.h", "csrc/masks.h",
+                             "csrc/fft_dev.h", "csrc/median47_core.h", "csrc/median_net.h"],
+                 file_flags={"blockrun_kernel.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-mllvm", "-amdgpu-use-amdgpu-trackers=1",
+                                                     "-DZEN_FFT_LDS_BARRIER", "-DZEN_FFT_FOLD_ADDR", "-Wno-unused-function"]})
+ENGINE_ADDONS = {blockrun.name: blockrun}                  # on the engine's own state
+ALL_ADDONS = {**ADDONS, **ENGINE_ADDONS}
 
 
 if __name__ == "__main__":
-    names = [a for a in sys.argv[1:] if not a.startswith("--")] or list(ADDONS)
+    names = [a for a in sys.argv[1:] if not a.startswith("--")] or list(ALL_ADDONS)
     for n in names:
-        ADDONS[n].build(force="--force" in sys.argv, verbose=True)
+        ALL_ADDONS[n].build(force="--force" in sys.argv, verbose=True)

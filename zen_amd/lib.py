@@ -207,8 +207,59 @@ def debug_poke(dev_ptr, byte_offset, value):
     _ck(load().zen_hip_debug_poke(dev_ptr, int(byte_offset), int(value) & 0xFFFFFFFF))
 
 
+# options under which a block call is the base library's alone: they select or instrument one of its own kernels
+_BASE_ONLY_OPTIONS = ("no_block_fused", "no_rt_fused", "no_direct_out", "mask_divide", "rt_fused_diag")
+_options = {}
+
+
 def set_option(name, value):
     _ck(load().zen_hip_set_option(name.encode(), int(value)))
+    _options[name] = int(value)
+
+
+# zen_amd/blockrun/zen_hip_blockrun.h: the headline block call with runs of hops per workgroup (libzen_hip_blockrun.so)
+BLOCKRUN_SYMBOLS = [
+    ("zen_hip_blockrun_process", _i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz]),
+    ("zen_hip_blockrun_set", _i, [C.c_char_p, _i]),
+    ("zen_hip_blockrun_stats", _i, [C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+]
+_blockrun = None
+
+
+def load_blockrun():
+    """libzen_hip_blockrun.so (built first where it is absent), or False where it cannot be had: HPR.process then calls the
+    base library, which computes the same.  A/B hook: ZEN_HIP_BLOCKRUN="off=1,run_len=4" -> zen_hip_blockrun_set."""
+    global _blockrun
+    if _blockrun is None:
+        import subprocess
+        from . import _addon
+        try:
+            _blockrun = _addon.load("blockrun", BLOCKRUN_SYMBOLS)
+        except (ImportError, OSError, RuntimeError, subprocess.CalledProcessError):
+            _blockrun = False
+        else:
+            for item in filter(None, os.environ.get("ZEN_HIP_BLOCKRUN", "").split(",")):
+                name, _, val = item.partition("=")
+                blockrun_set(name.strip(), int(val or 1))
+    return _blockrun
+
+
+def blockrun_set(key, value):
+    """zen_hip_blockrun_set: "run_len", "min_items", "off" (tests and A/B runs)."""
+    L = load_blockrun()
+    if not L:
+        raise ImportError("libzen_hip_blockrun.so is not built and cannot be built here")
+    _ck(L.zen_hip_blockrun_set(key.encode(), int(value)))
+
+
+def blockrun_stats():
+    """(calls the run kernel served, calls forwarded to the base library) since libzen_hip_blockrun.so was loaded."""
+    L = load_blockrun()
+    if not L:
+        raise ImportError("libzen_hip_blockrun.so is not built and cannot be built here")
+    a, b = C.c_ulonglong(), C.c_ulonglong()
+    _ck(L.zen_hip_blockrun_stats(C.byref(a), C.byref(b)))
+    return a.value, b.value
 
 
 def device_name():
@@ -430,7 +481,9 @@ class HPR:
     def process(self, in_dev, n_hops, in_stride=None, harm=None, perc=None, resid=None, out_stride=None):
         in_stride = n_hops * self.hop if in_stride is None else in_stride
         out_stride = n_hops * self.hop if out_stride is None else out_stride
-        _ck(load().zen_hip_hpr_process(self._h, in_dev, n_hops, in_stride, harm, perc, resid, out_stride))
+        run = None if any(_options.get(k) for k in _BASE_ONLY_OPTIONS) else load_blockrun()
+        f = run.zen_hip_blockrun_process if run else load().zen_hip_hpr_process
+        _ck(f(self._h, in_dev, n_hops, in_stride, harm, perc, resid, out_stride))
 
     def process_host(self, x, harm=None, perc=None, resid=None):
         """zen_hip_hpr_process_host: x and the wanted outputs are HOST float32 arrays of n_hops * hop samples (numpy arrays,
