@@ -1,13 +1,13 @@
 """Builds the add-on libraries for gfx950 with hipcc: zen_amd/libzen_hip_<name>.so from zen_amd/<name>/, each a library of
-its own on top of libzen_hip.so's C ABI (blockrun: on top of the engine's state as well), and the demo program zen_amd/bin/pitch-track (plain g++: it reaches the GPU through
-the two C ABIs only).
+its own on top of libzen_hip.so's C ABI (blockrun: on top of the engine's state as well), and the demo programs zen_amd/bin/pitch-track and zen_amd/bin/beat-track (plain
+g++: they reach the GPU through two C ABIs only).
 
     python zen_amd/addon_build.py [name ...] [--force]         # no name: all of them
 
 Every library links against libzen_hip.so (zen_amd/build.py builds that one first) and finds it beside itself ($ORIGIN).
 -ffp-contract=off and no fast-math flag, for all of them: every float operation of their kernels is a single IEEE operation,
 one rounding each -- the contract of pcm/pcm_convert.h (the division, the products and the rounding are those of the host
-code in zen_amd/cli/wav.h), the one add P1 + R1 of ragged and live, and DESIGN.md section 13 for pitch.
+code in zen_amd/cli/wav.h), the one add P1 + R1 of ragged and live, DESIGN.md section 13 for pitch and section 15 for beat (whose host tables are part of it).
 """
 import glob
 import os
@@ -92,6 +92,23 @@ def build_demo(verbose=False):
     return DEMO
 
 
+BEAT_DEMO = os.path.join(HERE, "bin", "beat-track")
+
+
+def build_beat_demo(verbose=False):
+    src, out = os.path.join(HERE, "beat"), os.path.join(HERE, "libzen_hip_beat.so")
+    srcs = [os.path.join(src, "beat_track.cpp"), os.path.join(src, "zen_hip_beat.h"), os.path.join(HERE, "cli", "wav.h"), out]
+    if os.path.exists(BEAT_DEMO) and os.path.getmtime(BEAT_DEMO) >= max(os.path.getmtime(p) for p in srcs):
+        return BEAT_DEMO
+    os.makedirs(os.path.dirname(BEAT_DEMO), exist_ok=True)
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
+                           "-I", src, "-I", os.path.join(HERE, "cli"), srcs[0], "-o", BEAT_DEMO, "-L", HERE, "-lzen_hip_beat", "-lzen_hip",
+                           "-Wl,-rpath,$ORIGIN/.."])
+    if verbose:
+        print("built", BEAT_DEMO)
+    return BEAT_DEMO
+
+
 pcm = Addon("pcm", ["pcm_kernels.hip", "pcm_pipe.hip"], extra_deps=["csrc/host_pipe.h"], title="PCM")
 ragged = Addon("ragged", ["ragged_kernels.hip", "ragged.hip"])
 live = Addon("live", ["live_kernels.hip", "live.hip"])
@@ -108,7 +125,10 @@ blockrun = Addon("blockrun", ["blockrun_kernel.hip", "blockrun.hip"],
                  file_flags={"blockrun_kernel.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-mllvm", "-amdgpu-use-amdgpu-trackers=1",
                                                      "-DZEN_FFT_LDS_BARRIER", "-DZEN_FFT_FOLD_ADDR", "-Wno-unused-function"]})
 ENGINE_ADDONS = {blockrun.name: blockrun}                  # on the engine's own state
-ALL_ADDONS = {**ADDONS, **ENGINE_ADDONS}
+# beat came after the four of ADDONS and is, like them, on the C ABI alone; beat_track.cpp is the demo's, not the library's
+beat = Addon("beat", ["beat_kernels.hip", "beat.hip"], build_demo=build_beat_demo)
+LATER_ADDONS = {beat.name: beat}
+ALL_ADDONS = {**ADDONS, **ENGINE_ADDONS, **LATER_ADDONS}
 
 
 if __name__ == "__main__":
