@@ -1,6 +1,6 @@
 """Builds the add-on libraries for gfx950 with hipcc: zen_amd/libzen_hip_<name>.so from zen_amd/<name>/, each a library of
-its own on top of libzen_hip.so's C ABI (blockrun: on top of the engine's state as well), and the demo programs zen_amd/bin/pitch-track and zen_amd/bin/beat-track (plain
-g++: they reach the GPU through two C ABIs only).
+its own on top of libzen_hip.so's C ABI (blockrun: on top of the engine's state as well), and the demo programs zen_amd/bin/pitch-track, zen_amd/bin/beat-track
+and zen_amd/bin/zen-stems (plain g++: they reach the GPU through two C ABIs only).
 
     python zen_amd/addon_build.py [name ...] [--force]         # no name: all of them
 
@@ -75,38 +75,37 @@ class Addon:
         return self.OUT
 
 
+def _build_demo(name, source, exe, verbose):
+    """zen_amd/bin/<exe> from zen_amd/<name>/<source>, against libzen_hip_<name>.so and libzen_hip.so; made again where the
+    source, the library's header, cli/wav.h or the library is newer."""
+    src, out = os.path.join(HERE, name), os.path.join(HERE, "libzen_hip_%s.so" % name)
+    srcs = [os.path.join(src, source), os.path.join(src, "zen_hip_%s.h" % name), os.path.join(HERE, "cli", "wav.h"), out]
+    if os.path.exists(exe) and os.path.getmtime(exe) >= max(os.path.getmtime(p) for p in srcs):
+        return exe
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
+                           "-I", src, "-I", os.path.join(HERE, "cli"), srcs[0], "-o", exe, "-L", HERE, "-lzen_hip_" + name, "-lzen_hip",
+                           "-Wl,-rpath,$ORIGIN/.."])
+    if verbose:
+        print("built", exe)
+    return exe
+
+
 DEMO = os.path.join(HERE, "bin", "pitch-track")
+BEAT_DEMO = os.path.join(HERE, "bin", "beat-track")
+STEMS_DEMO = os.path.join(HERE, "bin", "zen-stems")
 
 
 def build_demo(verbose=False):
-    src, out = os.path.join(HERE, "pitch"), os.path.join(HERE, "libzen_hip_pitch.so")
-    srcs = [os.path.join(src, "pitch_track.cpp"), os.path.join(src, "zen_hip_pitch.h"), os.path.join(HERE, "cli", "wav.h"), out]
-    if os.path.exists(DEMO) and os.path.getmtime(DEMO) >= max(os.path.getmtime(p) for p in srcs):
-        return DEMO
-    os.makedirs(os.path.dirname(DEMO), exist_ok=True)
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
-                           "-I", src, "-I", os.path.join(HERE, "cli"), srcs[0], "-o", DEMO, "-L", HERE, "-lzen_hip_pitch", "-lzen_hip",
-                           "-Wl,-rpath,$ORIGIN/.."])
-    if verbose:
-        print("built", DEMO)
-    return DEMO
-
-
-BEAT_DEMO = os.path.join(HERE, "bin", "beat-track")
+    return _build_demo("pitch", "pitch_track.cpp", DEMO, verbose)
 
 
 def build_beat_demo(verbose=False):
-    src, out = os.path.join(HERE, "beat"), os.path.join(HERE, "libzen_hip_beat.so")
-    srcs = [os.path.join(src, "beat_track.cpp"), os.path.join(src, "zen_hip_beat.h"), os.path.join(HERE, "cli", "wav.h"), out]
-    if os.path.exists(BEAT_DEMO) and os.path.getmtime(BEAT_DEMO) >= max(os.path.getmtime(p) for p in srcs):
-        return BEAT_DEMO
-    os.makedirs(os.path.dirname(BEAT_DEMO), exist_ok=True)
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
-                           "-I", src, "-I", os.path.join(HERE, "cli"), srcs[0], "-o", BEAT_DEMO, "-L", HERE, "-lzen_hip_beat", "-lzen_hip",
-                           "-Wl,-rpath,$ORIGIN/.."])
-    if verbose:
-        print("built", BEAT_DEMO)
-    return BEAT_DEMO
+    return _build_demo("beat", "beat_track.cpp", BEAT_DEMO, verbose)
+
+
+def build_stems_demo(verbose=False):
+    return _build_demo("multi", "multi_stems.cpp", STEMS_DEMO, verbose)
 
 
 pcm = Addon("pcm", ["pcm_kernels.hip", "pcm_pipe.hip"], extra_deps=["csrc/host_pipe.h"], title="PCM")
@@ -127,7 +126,10 @@ blockrun = Addon("blockrun", ["blockrun_kernel.hip", "blockrun.hip"],
 ENGINE_ADDONS = {blockrun.name: blockrun}                  # on the engine's own state
 # beat came after the four of ADDONS and is, like them, on the C ABI alone; beat_track.cpp is the demo's, not the library's
 beat = Addon("beat", ["beat_kernels.hip", "beat.hip"], build_demo=build_beat_demo)
-LATER_ADDONS = {beat.name: beat}
+# multi (interleaved multichannel audio through the engines' rows) shares the sample arithmetic of pcm/pcm_convert.h;
+# multi_stems.cpp is the demo's, not the library's
+multi = Addon("multi", ["multi_kernels.hip", "multi.hip"], extra_deps=["pcm/pcm_convert.h"], build_demo=build_stems_demo)
+LATER_ADDONS = {beat.name: beat, multi.name: multi}
 ALL_ADDONS = {**ADDONS, **ENGINE_ADDONS, **LATER_ADDONS}
 
 

@@ -134,6 +134,38 @@ namespace wav {
 		if (pad)
 			f.put(0);
 	}
+
+	// `pcm`: interleaved frames of `channels` samples that already are PCM16 (zen_amd/multi narrows on the device); the
+	// same 44-byte header with the channel count, the byte rate and the block size of `channels`
+	inline void encode_pcm16_interleaved(const std::vector<int16_t>& pcm, int channels, int sampleRate, const std::string& path)
+	{
+		std::ofstream f(path, std::ios::binary);
+		if (!f)
+			throw std::runtime_error("cannot write " + path);
+		const uint32_t data_bytes = (uint32_t)(pcm.size() * 2);
+		unsigned char h[44];
+		auto w32 = [&](int o, uint32_t v) { h[o] = v & 255; h[o + 1] = (v >> 8) & 255; h[o + 2] = (v >> 16) & 255; h[o + 3] = v >> 24; };
+		auto w16 = [&](int o, uint16_t v) { h[o] = v & 255; h[o + 1] = v >> 8; };
+		memcpy(h, "RIFF", 4);
+		w32(4, 36 + data_bytes);
+		memcpy(h + 8, "WAVEfmt ", 8);
+		w32(16, 16);
+		w16(20, 1);
+		w16(22, (uint16_t)channels);
+		w32(24, (uint32_t)sampleRate);
+		w32(28, (uint32_t)sampleRate * 2 * (uint32_t)channels);
+		w16(32, (uint16_t)(2 * channels));
+		w16(34, 16);
+		memcpy(h + 36, "data", 4);
+		w32(40, data_bytes);
+		f.write((const char*)h, 44);
+		std::vector<unsigned char> le(pcm.size() * 2); // little-endian whatever the host is
+		for (std::size_t i = 0; i < pcm.size(); ++i) {
+			le[2 * i] = (unsigned char)((uint16_t)pcm[i] & 255);
+			le[2 * i + 1] = (unsigned char)((uint16_t)pcm[i] >> 8);
+		}
+		f.write((const char*)le.data(), data_bytes);
+	}
 } // namespace wav
 } // namespace zen
 
