@@ -1,13 +1,13 @@
 """Builds the add-on libraries for gfx950 with hipcc: zen_amd/libzen_hip_<name>.so from zen_amd/<name>/, each a library of
-its own on top of libzen_hip.so's C ABI (blockrun: on top of the engine's state as well), and the demo programs zen_amd/bin/pitch-track, zen_amd/bin/beat-track
-and zen_amd/bin/zen-stems (plain g++: they reach the GPU through two C ABIs only).
+its own on top of libzen_hip.so's C ABI (blockrun: on top of the engine's state as well), and the demo programs zen_amd/bin/pitch-track, zen_amd/bin/beat-track,
+zen_amd/bin/zen-stems and zen_amd/bin/zen-repet (plain g++: they reach the GPU through two C ABIs only).
 
     python zen_amd/addon_build.py [name ...] [--force]         # no name: all of them
 
 Every library links against libzen_hip.so (zen_amd/build.py builds that one first) and finds it beside itself ($ORIGIN).
 -ffp-contract=off and no fast-math flag, for all of them: every float operation of their kernels is a single IEEE operation,
 one rounding each -- the contract of pcm/pcm_convert.h (the division, the products and the rounding are those of the host
-code in zen_amd/cli/wav.h), the one add P1 + R1 of ragged and live, DESIGN.md section 13 for pitch and section 15 for beat (whose host tables are part of it).
+code in zen_amd/cli/wav.h), the one add P1 + R1 of ragged and live, DESIGN.md section 13 for pitch, section 15 for beat and section 17 for repet (whose host tables are part of it).
 """
 import glob
 import os
@@ -94,6 +94,7 @@ def _build_demo(name, source, exe, verbose):
 DEMO = os.path.join(HERE, "bin", "pitch-track")
 BEAT_DEMO = os.path.join(HERE, "bin", "beat-track")
 STEMS_DEMO = os.path.join(HERE, "bin", "zen-stems")
+REPET_DEMO = os.path.join(HERE, "bin", "zen-repet")
 
 
 def build_demo(verbose=False):
@@ -106,6 +107,10 @@ def build_beat_demo(verbose=False):
 
 def build_stems_demo(verbose=False):
     return _build_demo("multi", "multi_stems.cpp", STEMS_DEMO, verbose)
+
+
+def build_repet_demo(verbose=False):
+    return _build_demo("repet", "repet_main.cpp", REPET_DEMO, verbose)
 
 
 pcm = Addon("pcm", ["pcm_kernels.hip", "pcm_pipe.hip"], extra_deps=["csrc/host_pipe.h"], title="PCM")
@@ -129,7 +134,9 @@ beat = Addon("beat", ["beat_kernels.hip", "beat.hip"], build_demo=build_beat_dem
 # multi (interleaved multichannel audio through the engines' rows) shares the sample arithmetic of pcm/pcm_convert.h;
 # multi_stems.cpp is the demo's, not the library's
 multi = Addon("multi", ["multi_kernels.hip", "multi.hip"], extra_deps=["pcm/pcm_convert.h"], build_demo=build_stems_demo)
-LATER_ADDONS = {beat.name: beat, multi.name: multi}
+# repet (repeating background against foreground) is on the C ABI alone as well; repet_main.cpp is the demo's, not the library's
+repet = Addon("repet", ["repet_kernels.hip", "repet.hip"], build_demo=build_repet_demo)
+LATER_ADDONS = {beat.name: beat, multi.name: multi, repet.name: repet}
 ALL_ADDONS = {**ADDONS, **ENGINE_ADDONS, **LATER_ADDONS}
 
 
