@@ -1,13 +1,13 @@
 """Builds the add-on libraries for gfx950 with hipcc: zen_amd/libzen_hip_<name>.so from zen_amd/<name>/, each a library of
 its own on top of libzen_hip.so's C ABI (blockrun: on top of the engine's state as well), and the demo programs zen_amd/bin/pitch-track, zen_amd/bin/beat-track,
-zen_amd/bin/zen-stems and zen_amd/bin/zen-repet (plain g++: they reach the GPU through two C ABIs only).
+zen_amd/bin/zen-stems, zen_amd/bin/zen-repet and zen_amd/bin/zen-cqt (plain g++: they reach the GPU through two C ABIs only).
 
     python zen_amd/addon_build.py [name ...] [--force]         # no name: all of them
 
 Every library links against libzen_hip.so (zen_amd/build.py builds that one first) and finds it beside itself ($ORIGIN).
 -ffp-contract=off and no fast-math flag, for all of them: every float operation of their kernels is a single IEEE operation,
 one rounding each -- the contract of pcm/pcm_convert.h (the division, the products and the rounding are those of the host
-code in zen_amd/cli/wav.h), the one add P1 + R1 of ragged and live, DESIGN.md section 13 for pitch, section 15 for beat and section 17 for repet (whose host tables are part of it).
+code in zen_amd/cli/wav.h), the one add P1 + R1 of ragged and live, DESIGN.md section 13 for pitch, section 15 for beat, section 17 for repet and section 18 for cqt (whose host tables are part of it).
 """
 import glob
 import os
@@ -95,6 +95,7 @@ DEMO = os.path.join(HERE, "bin", "pitch-track")
 BEAT_DEMO = os.path.join(HERE, "bin", "beat-track")
 STEMS_DEMO = os.path.join(HERE, "bin", "zen-stems")
 REPET_DEMO = os.path.join(HERE, "bin", "zen-repet")
+CQT_DEMO = os.path.join(HERE, "bin", "zen-cqt")
 
 
 def build_demo(verbose=False):
@@ -111,6 +112,10 @@ def build_stems_demo(verbose=False):
 
 def build_repet_demo(verbose=False):
     return _build_demo("repet", "repet_main.cpp", REPET_DEMO, verbose)
+
+
+def build_cqt_demo(verbose=False):
+    return _build_demo("cqt", "cqt_main.cpp", CQT_DEMO, verbose)
 
 
 pcm = Addon("pcm", ["pcm_kernels.hip", "pcm_pipe.hip"], extra_deps=["csrc/host_pipe.h"], title="PCM")
@@ -136,7 +141,9 @@ beat = Addon("beat", ["beat_kernels.hip", "beat.hip"], build_demo=build_beat_dem
 multi = Addon("multi", ["multi_kernels.hip", "multi.hip"], extra_deps=["pcm/pcm_convert.h"], build_demo=build_stems_demo)
 # repet (repeating background against foreground) is on the C ABI alone as well; repet_main.cpp is the demo's, not the library's
 repet = Addon("repet", ["repet_kernels.hip", "repet.hip"], build_demo=build_repet_demo)
-LATER_ADDONS = {beat.name: beat, multi.name: multi, repet.name: repet}
+# cqt (a sliced constant-Q transform and the separation in its domain) is on the C ABI alone too; cqt_main.cpp is the demo's
+cqt = Addon("cqt", ["cqt_kernels.hip", "cqt.hip"], build_demo=build_cqt_demo)
+LATER_ADDONS = {beat.name: beat, multi.name: multi, repet.name: repet, cqt.name: cqt}
 ALL_ADDONS = {**ADDONS, **ENGINE_ADDONS, **LATER_ADDONS}
 
 
