@@ -1,13 +1,13 @@
 """Builds the add-on libraries for gfx950 with hipcc: zen_amd/libzen_hip_<name>.so from zen_amd/<name>/, each a library of
 its own on top of libzen_hip.so's C ABI (blockrun: on top of the engine's state as well), and the demo programs zen_amd/bin/pitch-track, zen_amd/bin/beat-track,
-zen_amd/bin/zen-stems, zen_amd/bin/zen-repet and zen_amd/bin/zen-cqt (plain g++: they reach the GPU through two C ABIs only).
+zen_amd/bin/zen-stems, zen_amd/bin/zen-repet, zen_amd/bin/zen-cqt and zen_amd/bin/zen-repsim (plain g++: they reach the GPU through two C ABIs only).
 
     python zen_amd/addon_build.py [name ...] [--force]         # no name: all of them
 
 Every library links against libzen_hip.so (zen_amd/build.py builds that one first) and finds it beside itself ($ORIGIN).
 -ffp-contract=off and no fast-math flag, for all of them: every float operation of their kernels is a single IEEE operation,
 one rounding each -- the contract of pcm/pcm_convert.h (the division, the products and the rounding are those of the host
-code in zen_amd/cli/wav.h), the one add P1 + R1 of ragged and live, DESIGN.md section 13 for pitch, section 15 for beat, section 17 for repet and section 18 for cqt (whose host tables are part of it).
+code in zen_amd/cli/wav.h), the one add P1 + R1 of ragged and live, DESIGN.md section 13 for pitch, section 15 for beat, section 17 for repet, section 18 for cqt (whose host tables are part of it) and section 19 for repsim.
 """
 import glob
 import os
@@ -96,6 +96,7 @@ BEAT_DEMO = os.path.join(HERE, "bin", "beat-track")
 STEMS_DEMO = os.path.join(HERE, "bin", "zen-stems")
 REPET_DEMO = os.path.join(HERE, "bin", "zen-repet")
 CQT_DEMO = os.path.join(HERE, "bin", "zen-cqt")
+REPSIM_DEMO = os.path.join(HERE, "bin", "zen-repsim")
 
 
 def build_demo(verbose=False):
@@ -116,6 +117,10 @@ def build_repet_demo(verbose=False):
 
 def build_cqt_demo(verbose=False):
     return _build_demo("cqt", "cqt_main.cpp", CQT_DEMO, verbose)
+
+
+def build_repsim_demo(verbose=False):
+    return _build_demo("repsim", "repsim_main.cpp", REPSIM_DEMO, verbose)
 
 
 pcm = Addon("pcm", ["pcm_kernels.hip", "pcm_pipe.hip"], extra_deps=["csrc/host_pipe.h"], title="PCM")
@@ -143,7 +148,10 @@ multi = Addon("multi", ["multi_kernels.hip", "multi.hip"], extra_deps=["pcm/pcm_
 repet = Addon("repet", ["repet_kernels.hip", "repet.hip"], build_demo=build_repet_demo)
 # cqt (a sliced constant-Q transform and the separation in its domain) is on the C ABI alone too; cqt_main.cpp is the demo's
 cqt = Addon("cqt", ["cqt_kernels.hip", "cqt.hip"], build_demo=build_cqt_demo)
-LATER_ADDONS = {beat.name: beat, multi.name: multi, repet.name: repet, cqt.name: cqt}
+# repsim (REPET-SIM: the repeating background found from the similarity matrix, the tree's one matrix-core kernel) is on the C
+# ABI alone as well; repsim_main.cpp is the demo's
+repsim = Addon("repsim", ["repsim_kernels.hip", "repsim.hip"], build_demo=build_repsim_demo)
+LATER_ADDONS = {beat.name: beat, multi.name: multi, repet.name: repet, cqt.name: cqt, repsim.name: repsim}
 ALL_ADDONS = {**ADDONS, **ENGINE_ADDONS, **LATER_ADDONS}
 
 
