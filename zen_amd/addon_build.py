@@ -1,13 +1,13 @@
 """Builds the add-on libraries for gfx950 with hipcc: zen_amd/libzen_hip_<name>.so from zen_amd/<name>/, each a library of
 its own on top of libzen_hip.so's C ABI (blockrun: on top of the engine's state as well), and the demo programs zen_amd/bin/pitch-track, zen_amd/bin/beat-track,
-zen_amd/bin/zen-stems, zen_amd/bin/zen-repet, zen_amd/bin/zen-cqt and zen_amd/bin/zen-repsim (plain g++: they reach the GPU through two C ABIs only).
+zen_amd/bin/zen-stems, zen_amd/bin/zen-repet, zen_amd/bin/zen-cqt, zen_amd/bin/zen-repsim and zen_amd/bin/zen-nmf (plain g++: they reach the GPU through two C ABIs only).
 
     python zen_amd/addon_build.py [name ...] [--force]         # no name: all of them
 
 Every library links against libzen_hip.so (zen_amd/build.py builds that one first) and finds it beside itself ($ORIGIN).
 -ffp-contract=off and no fast-math flag, for all of them: every float operation of their kernels is a single IEEE operation,
 one rounding each -- the contract of pcm/pcm_convert.h (the division, the products and the rounding are those of the host
-code in zen_amd/cli/wav.h), the one add P1 + R1 of ragged and live, DESIGN.md section 13 for pitch, section 15 for beat, section 17 for repet, section 18 for cqt (whose host tables are part of it) and section 19 for repsim.
+code in zen_amd/cli/wav.h), the one add P1 + R1 of ragged and live, DESIGN.md section 13 for pitch, section 15 for beat, section 17 for repet, section 18 for cqt (whose host tables are part of it), section 19 for repsim and section 20 for nmf.
 """
 import glob
 import os
@@ -97,6 +97,7 @@ STEMS_DEMO = os.path.join(HERE, "bin", "zen-stems")
 REPET_DEMO = os.path.join(HERE, "bin", "zen-repet")
 CQT_DEMO = os.path.join(HERE, "bin", "zen-cqt")
 REPSIM_DEMO = os.path.join(HERE, "bin", "zen-repsim")
+NMF_DEMO = os.path.join(HERE, "bin", "zen-nmf")
 
 
 def build_demo(verbose=False):
@@ -121,6 +122,10 @@ def build_cqt_demo(verbose=False):
 
 def build_repsim_demo(verbose=False):
     return _build_demo("repsim", "repsim_main.cpp", REPSIM_DEMO, verbose)
+
+
+def build_nmf_demo(verbose=False):
+    return _build_demo("nmf", "nmf_main.cpp", NMF_DEMO, verbose)
 
 
 pcm = Addon("pcm", ["pcm_kernels.hip", "pcm_pipe.hip"], extra_deps=["csrc/host_pipe.h"], title="PCM")
@@ -152,7 +157,11 @@ cqt = Addon("cqt", ["cqt_kernels.hip", "cqt.hip"], build_demo=build_cqt_demo)
 # ABI alone as well; repsim_main.cpp is the demo's
 repsim = Addon("repsim", ["repsim_kernels.hip", "repsim.hip"], build_demo=build_repsim_demo)
 LATER_ADDONS = {beat.name: beat, multi.name: multi, repet.name: repet, cqt.name: cqt, repsim.name: repsim}
-ALL_ADDONS = {**ADDONS, **ENGINE_ADDONS, **LATER_ADDONS}
+# nmf (supervised factorisation of the magnitude spectrogram: three matrix products per iteration on the matrix cores) came
+# after the five of LATER_ADDONS and is, like them, on the C ABI alone; nmf_main.cpp is the demo's
+nmf = Addon("nmf", ["nmf_kernels.hip", "nmf.hip"], build_demo=build_nmf_demo)
+FACTOR_ADDONS = {nmf.name: nmf}
+ALL_ADDONS = {**ADDONS, **ENGINE_ADDONS, **LATER_ADDONS, **FACTOR_ADDONS}
 
 
 if __name__ == "__main__":
