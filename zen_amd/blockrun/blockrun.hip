@@ -4,11 +4,13 @@
 // of the two libraries served a call, and neither can the call after it.
 #include "../csrc/hpr_engine.h"
 #include "../csrc/masks.h"
+#include "blockrun_first_pass.h"
 #include "blockrun_kernel.h"
 #include "zen_hip_blockrun.h"
 
 #include <atomic>
 #include <cstring>
+#include <vector>
 
 using namespace zen_hip_impl;
 
@@ -67,6 +69,30 @@ int device_slots(int* slots)
 	return ZEN_HIP_OK;
 }
 
+// Whether the engine's twiddle table (every engine of nfft 4096 builds the same one: make_twiddles, csrc/api.hip) has the
+// symmetry the first pass's conjugate shortcut relies on -- checked on the host table, once, before the first launch of the
+// run kernel; without it the launch takes the kernel that computes every output of the first pass (blockrun_first_pass.h).
+// With it the three entries that pass multiplies with, taken from the same host table.
+struct FirstPassTable {
+	int symmetric;
+	float2 tw16, tw8, tw3_16; // tw[N/16], tw[N/8], tw[3N/16]
+};
+const FirstPassTable& first_pass_table()
+{
+	static const FirstPassTable t = [] {
+		constexpr int n = zen_blockrun::NFFT;
+		std::vector<float> tw(n);
+		make_twiddles(tw.data(), tw.size());
+		FirstPassTable r;
+		r.symmetric = zen_blockrun::table_is_symmetric(tw.data(), n) ? 1 : 0;
+		r.tw16 = make_float2(tw[2 * (n / 16)], tw[2 * (n / 16) + 1]);
+		r.tw8 = make_float2(tw[2 * (n / 8)], tw[2 * (n / 8) + 1]);
+		r.tw3_16 = make_float2(tw[2 * (3 * n / 16)], tw[2 * (3 * n / 16) + 1]);
+		return r;
+	}();
+	return t;
+}
+
 bool takes(const zen_hip_hpr* h, const float* in, size_t n_hops, size_t in_stride, const float* harm, const float* perc,
            const float* resid, size_t out_stride)
 {
@@ -117,6 +143,14 @@ extern "C" int zen_hip_blockrun_process(zen_hip_hpr_t h, const float* in_dev, si
 	a.tail_next = h->d_tail[h->tail_sel ^ 1];
 	a.window = h->d_window;
 	a.tw = h->d_tw;
+	{
+		// the three entries the first analysis pass multiplies with travel as arguments: the same for every thread and frame
+		const FirstPassTable& t = first_pass_table();
+		a.tw_symmetric = t.symmetric;
+		a.tw16 = t.tw16;
+		a.tw8 = t.tw8;
+		a.tw3_16 = t.tw3_16;
+	}
 	a.mag = h->d_mag;
 	a.keep_mag_rows = (int)h->W - 1;
 	a.ring_rows = h->ring_rows;

@@ -17,6 +17,8 @@ struct RunArgs {
 	float* tail_next;       // receives the call's last hop
 	const float* window;    // HOP * 2 values
 	const float2* tw;
+	int tw_symmetric;       // the host table passed blockrun_first_pass.h's table_is_symmetric (the engine's does)
+	float2 tw16, tw8, tw3_16; // tw[N/16], tw[N/8], tw[3N/16] of the host table: all the first analysis pass multiplies with
 	float* mag;             // magnitude ring: the call's last keep_mag_rows frames store their rows
 	int keep_mag_rows;
 	long long ring_rows, row0;

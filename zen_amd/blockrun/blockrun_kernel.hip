@@ -20,6 +20,7 @@
 #include "../csrc/median47_core.h"
 #include "../csrc/median_net.h"
 #include "blockrun_kernel.h"
+#include "blockrun_first_pass.h"
 
 #pragma clang fp contract(off)
 
@@ -34,6 +35,9 @@ static_assert(N == NFFT && TF == 256 && HOP == 4 * TF, "four samples of a hop pe
 // the magnitude image of the median stage: 16-word chunks 20 words apart, column k at word k + 24 (median47_core.h)
 constexpr int MID = TAPS / 2, MID_AL = 24, IMG_END = 255 * 16 + 64;
 __device__ __forceinline__ int img_addr(int g) { return (g >> 4) * zm47::RSTR + (g & 15); }
+// the mirrored columns the median stage reads: those of bins 1 .. MIR_LO and N/2 - MIR_HI .. N/2 - 1 (FwdOut)
+constexpr int MIR_LO = 56, MIR_HI = 39;
+static_assert(N - MIR_LO <= 16 * 254 - 24 && N / 2 + MIR_HI >= 16 * 128 + 39, "blocks 254 / 255 and 126 .. 128 read written columns");
 // rt_fused.hip's lean layout inside the frame image: the compact P row and the wave-edge records
 constexpr int PC_WORD = 5184, PC_TAIL = 2052, EDGE_WORD = PC_WORD + PC_TAIL + 512 + 4;
 static_assert((EDGE_WORD + 256) * 4 <= PL::LDS_FLOAT2 * 8, "lean layout must fit in the frame image");
@@ -71,7 +75,17 @@ struct FwdInPre { // rt_fused.hip: the eight samples and window values of the th
 	__device__ __forceinline__ float2 operator()(int, int slot) const { return make_float2(x[slot] * w[slot], 0.0f); } // window_functor hps.h:24-33
 };
 
-struct FwdOut { // rt_fused.hip FwdOut<16, 256> without the rings (the magnitude ring's rows are copied from the image)
+// rt_fused.hip FwdOut<16, 256> without the rings (the magnitude ring's rows are copied from the image) and without the
+// mirrored columns nobody reads.  The median stage produces columns 0 .. 2051 and 4073 .. 4095 of the P row (InvIn); a
+// block t reads columns 16t - 24 .. 16t + 39, so of the upper half of the row
+//   blocks 126 / 127 (waves 1's last lanes) read up to column 2055 / 2071 (the edge record of blocks 128 and 129, chunk 130),
+//   block 128 reads 2024 .. 2087 (its neighbours 129 and 130 by DPP, chunk 131),
+//   blocks 254 and 255 read 4040 .. 4095 and the border (blocks 253 .. 255; block 253's pieces are made of 4040 .. 4055),
+// that is the mirrors of bins 2009 .. 2047 (slot 7, tf >= 217) and 1 .. 56 (slot 0, 1 <= tf <= 56); the border replica takes
+// column 4095.  Wave 2's other lanes (blocks 129 .. 159, 224 .. 252) are parked: they sort whatever the image holds there
+// (words of the image, never outside it) and their medians are not read.  InvIn and the magnitude rows take |S[k]| of the
+// upper half from the mirrored lower column.
+struct FwdOut {
 	Spec* r;
 	int* img;
 	__device__ __forceinline__ void operator()(int idx, float2 X, bool lower, int slot) const
@@ -82,9 +96,11 @@ struct FwdOut { // rt_fused.hip FwdOut<16, 256> without the rings (the magnitude
 			const int key = __float_as_int(m);
 			constexpr int CH = (TF / 16) * zm47::RSTR;
 			const int tfl = idx - slot * TF;
-			const int a0 = img_addr(tfl + MID_AL), a1 = img_addr(N - tfl + MID_AL);
-			img[a0 + slot * CH] = key;
-			img[(idx == 0 || idx == (N >> 1)) ? a0 + slot * CH : a1 - slot * CH] = key;
+			img[img_addr(tfl + MID_AL) + slot * CH] = key;
+			if (slot == 0 && tfl >= 1 && tfl <= MIR_LO)
+				img[img_addr(N - tfl + MID_AL)] = key;
+			if (slot == 7 && tfl >= TF - MIR_HI)
+				img[img_addr(N - 7 * TF - tfl + MID_AL)] = key;
 		}
 	}
 };
@@ -104,8 +120,10 @@ struct InvIn { // rt_fused.hip InvInLean<4096, 256, 23, true>
 			pi = N - idx;
 		else
 			pi = (idx > N / 2 && idx < N - MID) ? N - idx : (idx > N / 2 ? idx - (N - 512) + PC_TAIL : idx);
-		const int g0 = idx + 24 - slot * TF;
-		const float mag = __int_as_float(img[(g0 >> 4) * 20 + (g0 & 15) + slot * (TF / 16) * 20]);
+		// |S[idx]|: column idx of the image, for the upper half of the Hermitian row column N - idx (FwdOut)
+		// (N - idx = (15 - slot) * TF + TF - tf: one base per half, the slot in the instruction's offset)
+		const int g0 = hi <= N / 2 ? idx + 24 - slot * TF : TF + 24 - (idx - slot * TF);
+		const float mag = __int_as_float(img[(g0 >> 4) * 20 + (g0 & 15) + (hi <= N / 2 ? slot : 15 - slot) * (TF / 16) * 20]);
 		const float2 z = r->S[slot];
 		const float m = hard_mask_exact(pc[pi], mag + FLT_EPSILON, thr);
 		return make_float2(z.x * m, z.y * m); // apply_mask_functor hps.h:58-66
@@ -132,7 +150,9 @@ struct InvOut {
 	}
 };
 
-__global__ __launch_bounds__(256, 3) void blockrun_kernel(RunArgs a)
+// SYM: the twiddle table has the symmetry first_pass16's conjugate shortcut needs (blockrun_first_pass.h)
+template <bool SYM>
+__device__ __forceinline__ void run_body(const RunArgs& a)
 {
 	extern __shared__ float2 lds[];
 	int* img = reinterpret_cast<int*>(lds);
@@ -238,16 +258,30 @@ __global__ __launch_bounds__(256, 3) void blockrun_kernel(RunArgs a)
 			FwdOut out;
 			out.r = &r;
 			out.img = img;
-			zfft::PassRunner<12, 0, false, true, false, FwdInPre, FwdOut, false, TwGlobal32>::run(tf, lds, TwGlobal32{tw}, pre, out, true);
+			// pass 0 as the real 16-point transform it is (blockrun_first_pass.h), its results where PassRunner<12, 0, ...>
+			// puts them (autosort layout: output c of thread tf at element tf + c * N/16); the runner goes on from pass 1
+			{
+				float p[8];
+#pragma unroll
+				for (int m = 0; m < 8; ++m)
+					p[m] = pre.x[m] * pre.w[m]; // window_functor hps.h:24-33
+				float2 Y0[16];
+				first_pass16<true, SYM>(p, a.tw16, a.tw8, a.tw3_16, Y0); // (the table's entries as arguments: scalar registers)
+#pragma unroll
+				for (int c = 0; c < 16; ++c)
+					lds[PL::pad_off(tf, c * (N / 16))] = Y0[c];
+				zfft::frame_sync<TF>();
+			}
+			zfft::PassRunner<12, 1, false, true, false, FwdInPre, FwdOut, false, TwGlobal32>::run(tf, lds, TwGlobal32{tw}, pre, out, true);
 		}
 		lds_barrier();
 		// A later use_sse_filter() reads the magnitude rows of the stft_width-1 frames before it: the call's last frames store
-		// theirs, from the image (column k at word k + 24 holds the bits of |S[k]|, both halves of the Hermitian row)
+		// theirs, from the image (column k at word k + 24 holds the bits of |S[k]|, k <= N/2; the upper half of the Hermitian row mirrors it)
 		if (f >= a.n_frames - a.keep_mag_rows) {
 			float* mag = a.mag + (((a.row0 + f) % a.ring_rows) + (long long)s * a.ring_rows) * N;
 			for (int g = tf; g < N; g += TF) {
 				ZH_CHK(mag + g, 1);
-				mag[g] = __int_as_float(img[img_addr(g + MID_AL)]);
+				mag[g] = __int_as_float(img[img_addr((g <= N / 2 ? g : N - g) + MID_AL)]);
 			}
 		}
 		// replicate border of the magnitude row (ippBorderRepl)
@@ -319,6 +353,10 @@ __global__ __launch_bounds__(256, 3) void blockrun_kernel(RunArgs a)
 	}
 }
 
+__global__ __launch_bounds__(256, 3) void blockrun_kernel(RunArgs a) { run_body<true>(a); }
+// the same for a table without the symmetry: outputs 9 .. 15 of the first pass computed one by one
+__global__ __launch_bounds__(256, 3) void blockrun_kernel_plain_table(RunArgs a) { run_body<false>(a); }
+
 // the hops the run kernel left: out = (previous frame's second half, or the carry for the first hop of the call) + this
 // frame's first half -- rt_fused.hip's fix-up for one output; one wavefront per item, all marks read side by side
 __global__ __launch_bounds__(256) void blockrun_fixup_kernel(RunArgs a)
@@ -373,7 +411,10 @@ size_t run_kernel_lds_bytes() { return LDS_BYTES; }
 int launch_run(const RunArgs& a, hipStream_t stream)
 {
 	const long long runs = (long long)a.n_streams * a.part.runs_per_stream;
-	hipLaunchKernelGGL(blockrun_kernel, dim3((unsigned)runs), dim3(TF), LDS_BYTES, stream, a);
+	if (a.tw_symmetric)
+		hipLaunchKernelGGL(blockrun_kernel, dim3((unsigned)runs), dim3(TF), LDS_BYTES, stream, a);
+	else
+		hipLaunchKernelGGL(blockrun_kernel_plain_table, dim3((unsigned)runs), dim3(TF), LDS_BYTES, stream, a);
 	ZH_HIP(hipGetLastError());
 	return ZEN_HIP_OK;
 }
