@@ -21,6 +21,7 @@
 #include "../csrc/median_net.h"
 #include "blockrun_kernel.h"
 #include "blockrun_first_pass.h"
+#include "blockrun_edge_count.h"
 
 #pragma clang fp contract(off)
 
@@ -38,6 +39,7 @@ __device__ __forceinline__ int img_addr(int g) { return (g >> 4) * zm47::RSTR + 
 // the mirrored columns the median stage reads: those of bins 1 .. MIR_LO and N/2 - MIR_HI .. N/2 - 1 (FwdOut)
 constexpr int MIR_LO = 56, MIR_HI = 39;
 static_assert(N - MIR_LO <= 16 * 254 - 24 && N / 2 + MIR_HI >= 16 * 128 + 39, "blocks 254 / 255 and 126 .. 128 read written columns");
+static_assert(EDGE_IMG_COL0 == MID_AL && EDGE_IMG_RSTR == zm47::RSTR && EDGE_OUTPUTS == MID + 1, "blockrun_edge_count.h reads this image");
 // rt_fused.hip's lean layout inside the frame image: the compact P row and the wave-edge records
 constexpr int PC_WORD = 5184, PC_TAIL = 2052, EDGE_WORD = PC_WORD + PC_TAIL + 512 + 4;
 static_assert((EDGE_WORD + 256) * 4 <= PL::LDS_FLOAT2 * 8, "lean layout must fit in the frame image");
@@ -76,22 +78,26 @@ struct FwdInPre { // rt_fused.hip: the eight samples and window values of the th
 };
 
 // rt_fused.hip FwdOut<16, 256> without the rings (the magnitude ring's rows are copied from the image) and without the
-// mirrored columns nobody reads.  The median stage produces columns 0 .. 2051 and 4073 .. 4095 of the P row (InvIn); a
-// block t reads columns 16t - 24 .. 16t + 39, so of the upper half of the row
-//   blocks 126 / 127 (waves 1's last lanes) read up to column 2055 / 2071 (the edge record of blocks 128 and 129, chunk 130),
-//   block 128 reads 2024 .. 2087 (its neighbours 129 and 130 by DPP, chunk 131),
-//   blocks 254 and 255 read 4040 .. 4095 and the border (blocks 253 .. 255; block 253's pieces are made of 4040 .. 4055),
-// that is the mirrors of bins 2009 .. 2047 (slot 7, tf >= 217) and 1 .. 56 (slot 0, 1 <= tf <= 56); the border replica takes
-// column 4095.  Wave 2's other lanes (blocks 129 .. 159, 224 .. 252) are parked: they sort whatever the image holds there
-// (words of the image, never outside it) and their medians are not read.  InvIn and the magnitude rows take |S[k]| of the
-// upper half from the mirrored lower column.
+// mirrored columns nobody reads.  The median stage selects columns 0 .. 2047 of the P row (blocks 0 .. 127, waves 0 and 1)
+// and counts the masks of columns 2048 and 4073 .. 4095 from the lower half (blockrun_edge_count.h, wave 3); a block t reads
+// columns 16t - 24 .. 16t + 39, so of the upper half of the row blocks 126 / 127 (wave 1's last lanes) read up to column
+// 2055 / 2071 (the edge record of blocks 128 and 129, sorted by wave 2's lanes 0 and 1; chunk 130): the mirrors of bins
+// 2025 .. 2047.  The stores cover more (bins 2009 .. 2047: slot 7, tf >= 217; bins 1 .. 56: slot 0, 1 <= tf <= 56, and the
+// border replica of column 4095), as when a third median stream read them.  Wave 2's other lanes (blocks 130 .. 191) sort
+// whatever the image holds there (words of the image, never outside it) and their records are not read.  InvIn and the
+// magnitude rows take |S[k]| of the upper half from the mirrored lower column.  Bin N/2 belongs to thread 0 alone.
 struct FwdOut {
 	Spec* r;
 	int* img;
 	__device__ __forceinline__ void operator()(int idx, float2 X, bool lower, int slot) const
 	{
 		r->S[slot] = X;
-		if (lower || idx == (N >> 1)) {
+		if (slot == 8) {
+			// bin N/2 is thread 0's alone: a branch waves 1 .. 3 skip, not a magnitude every thread computes and drops
+			if (__builtin_amdgcn_readfirstlane(idx) < (N >> 1) + 64 && idx == (N >> 1))
+				img[img_addr((N >> 1) + MID_AL)] = __float_as_int(zfft::cabs_exact(X.x, X.y));
+		}
+		else if (lower) {
 			const float m = zfft::cabs_exact(X.x, X.y); // complex_abs_functor hps.h:82-89
 			const int key = __float_as_int(m);
 			constexpr int CH = (TF / 16) * zm47::RSTR;
@@ -125,7 +131,11 @@ struct InvIn { // rt_fused.hip InvInLean<4096, 256, 23, true>
 		const int g0 = hi <= N / 2 ? idx + 24 - slot * TF : TF + 24 - (idx - slot * TF);
 		const float mag = __int_as_float(img[(g0 >> 4) * 20 + (g0 & 15) + (hi <= N / 2 ? slot : 15 - slot) * (TF / 16) * 20]);
 		const float2 z = r->S[slot];
-		const float m = hard_mask_exact(pc[pi], mag + FLT_EPSILON, thr);
+		const float p = pc[pi];
+		float m = hard_mask_exact(p, mag + FLT_EPSILON, thr);
+		// bin N/2 and the bins N - 23 .. N - 1: the word holds the mask itself (blockrun_edge_count.h), slots 8 and 15 only
+		if (hi > N / 2 && !(lo > N / 2 && hi < N - MID))
+			m = (idx == N / 2 || idx >= N - MID) ? p : m;
 		return make_float2(z.x * m, z.y * m); // apply_mask_functor hps.h:58-66
 	}
 };
@@ -293,28 +303,29 @@ __device__ __forceinline__ void run_body(const RunArgs& a)
 				img[img_addr(g)] = v1;
 		}
 		lds_barrier();
-		// ---- percussive estimate: frequency-direction median of the row (hps.cu:496), rt_fused.hip's block assignment:
-		// waves 0 and 1 filter blocks 0..127, wave 2 blocks 128..159 and 224..255, wave 3 sits the stage out
+		// ---- percussive estimate: frequency-direction median of the row (hps.cu:496).  Waves 0 and 1 filter blocks 0 .. 127.
+		// Wave 2 sorts blocks 128 .. 191 for the edge record of wave 1's last lanes (the sorted block 128 and the pieces of
+		// blocks 128 and 129; its other lanes' records are not read) and selects nothing.  Wave 3 counts the masks of bin N/2
+		// and of the bins N - 23 .. N - 1 while the others sort (blockrun_edge_count.h): InvIn reads them as they stand.
 		{
 			int(*edge)[64] = reinterpret_cast<int(*)[64]>(img + EDGE_WORD);
 			const int lane = tf & 63, wave = __builtin_amdgcn_readfirstlane(tf >> 6);
-			const int blk = wave < 2 ? tf : (lane < 32 ? 128 + lane : 192 + lane);
 			zm47::Pieces pc;
-			if (wave < 3)
-				zm47::m47_sort_and_publish(img, edge, blk, lane, wave, tf == 0, blk == 255, pc);
-			lds_barrier();
 			if (wave < 3) {
+				zm47::m47_sort_and_publish(img, edge, tf, lane, wave, tf == 0, false, pc);
+			}
+			else {
+				const unsigned bits = edge_count_wave(img, lane, a.thr, N / 2);
+				if (lane < EDGE_OUTPUTS)
+					Prow[lane == 0 ? N / 2 : PC_TAIL + 512 - lane] = (bits >> lane) & 1u ? 1.0f : 0.0f;
+			}
+			lds_barrier();
+			if (wave < 2) {
 				int o[16];
-				zm47::m47_select(img, edge, blk, wave, pc, o);
-				const int at = blk >= 224 ? PC_TAIL + (blk - 224) * 16 : blk * 16; // compact half row: bins 0..2051 and 3584..4095
-				if (blk <= 127 || blk >= 224) {
+				zm47::m47_select(img, edge, tf, wave, pc, o);
 #pragma unroll
-					for (int v = 0; v < 4; ++v)
-						*reinterpret_cast<int4*>(&Prow[at + 4 * v]) = make_int4(o[4 * v], o[4 * v + 1], o[4 * v + 2], o[4 * v + 3]);
-				}
-				else if (blk == 128) {
-					*reinterpret_cast<int4*>(&Prow[at]) = make_int4(o[0], o[1], o[2], o[3]);
-				}
+				for (int v = 0; v < 4; ++v)
+					*reinterpret_cast<int4*>(&Prow[tf * 16 + 4 * v]) = make_int4(o[4 * v], o[4 * v + 1], o[4 * v + 2], o[4 * v + 3]);
 			}
 		}
 		lds_barrier(); // P row complete
