@@ -1,13 +1,13 @@
 """Builds the add-on libraries for gfx950 with hipcc: zen_amd/libzen_hip_<name>.so from zen_amd/<name>/, each a library of
 its own on top of libzen_hip.so's C ABI (blockrun: on top of the engine's state as well), and the demo programs zen_amd/bin/pitch-track, zen_amd/bin/beat-track,
-zen_amd/bin/zen-stems, zen_amd/bin/zen-repet, zen_amd/bin/zen-cqt, zen_amd/bin/zen-repsim and zen_amd/bin/zen-nmf (plain g++: they reach the GPU through two C ABIs only).
+zen_amd/bin/zen-stems, zen_amd/bin/zen-repet, zen_amd/bin/zen-cqt, zen_amd/bin/zen-repsim, zen_amd/bin/zen-nmf and zen_amd/bin/zen-stretch (plain g++: they reach the GPU through two C ABIs only).
 
     python zen_amd/addon_build.py [name ...] [--force]         # no name: all of them
 
 Every library links against libzen_hip.so (zen_amd/build.py builds that one first) and finds it beside itself ($ORIGIN).
 -ffp-contract=off and no fast-math flag, for all of them: every float operation of their kernels is a single IEEE operation,
 one rounding each -- the contract of pcm/pcm_convert.h (the division, the products and the rounding are those of the host
-code in zen_amd/cli/wav.h), the one add P1 + R1 of ragged and live, DESIGN.md section 13 for pitch, section 15 for beat, section 17 for repet, section 18 for cqt (whose host tables are part of it), section 19 for repsim and section 20 for nmf.
+code in zen_amd/cli/wav.h), the one add P1 + R1 of ragged and live, DESIGN.md section 13 for pitch, section 15 for beat, section 17 for repet, section 18 for cqt (whose host tables are part of it), section 19 for repsim, section 20 for nmf and section 21 for tsm (whose host tables are part of it).
 """
 import glob
 import os
@@ -98,6 +98,7 @@ REPET_DEMO = os.path.join(HERE, "bin", "zen-repet")
 CQT_DEMO = os.path.join(HERE, "bin", "zen-cqt")
 REPSIM_DEMO = os.path.join(HERE, "bin", "zen-repsim")
 NMF_DEMO = os.path.join(HERE, "bin", "zen-nmf")
+STRETCH_DEMO = os.path.join(HERE, "bin", "zen-stretch")
 
 
 def build_demo(verbose=False):
@@ -126,6 +127,10 @@ def build_repsim_demo(verbose=False):
 
 def build_nmf_demo(verbose=False):
     return _build_demo("nmf", "nmf_main.cpp", NMF_DEMO, verbose)
+
+
+def build_stretch_demo(verbose=False):
+    return _build_demo("tsm", "tsm_main.cpp", STRETCH_DEMO, verbose)
 
 
 pcm = Addon("pcm", ["pcm_kernels.hip", "pcm_pipe.hip"], extra_deps=["csrc/host_pipe.h"], title="PCM")
@@ -162,9 +167,15 @@ LATER_ADDONS = {beat.name: beat, multi.name: multi, repet.name: repet, cqt.name:
 nmf = Addon("nmf", ["nmf_kernels.hip", "nmf.hip"], build_demo=build_nmf_demo)
 FACTOR_ADDONS = {nmf.name: nmf}
 ALL_ADDONS = {**ADDONS, **ENGINE_ADDONS, **LATER_ADDONS, **FACTOR_ADDONS}
+# tsm (time-scale modification: the harmonic stem through a phase-locked vocoder, the percussive one through overlap-add) is on
+# the C ABI alone as well; tsm_main.cpp is the demo's.  It has a table of its own: the eleven of ALL_ADDONS are the ones from
+# before it, and EVERY_ADDON is the lookup of the loader and of the command line.
+tsm = Addon("tsm", ["tsm_kernels.hip", "tsm.hip"], build_demo=build_stretch_demo)
+STRETCH_ADDONS = {tsm.name: tsm}
+EVERY_ADDON = {**ALL_ADDONS, **STRETCH_ADDONS}
 
 
 if __name__ == "__main__":
-    names = [a for a in sys.argv[1:] if not a.startswith("--")] or list(ALL_ADDONS)
+    names = [a for a in sys.argv[1:] if not a.startswith("--")] or list(EVERY_ADDON)
     for n in names:
-        ALL_ADDONS[n].build(force="--force" in sys.argv, verbose=True)
+        EVERY_ADDON[n].build(force="--force" in sys.argv, verbose=True)
