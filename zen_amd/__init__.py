@@ -11,4 +11,4 @@ from .lib import (  # noqa: F401
     ZenHipError, ZgException, blockrun_set, blockrun_stats, debug_poke, device_name, init, load, memcheck, run_plan, set_option, synchronize,
 )
 # the add-on builders under the names their four modules had: `from zen_amd import pcm_build` keeps working
-from .addon_build import beat as beat_build, cqt as cqt_build, live as live_build, multi as multi_build, nmf as nmf_build, pcm as pcm_build, pitch as pitch_build, ragged as ragged_build, repet as repet_build, repsim as repsim_build, tsm as tsm_build  # noqa: F401,E402
+from .addon_build import beat as beat_build, cqt as cqt_build, live as live_build, multi as multi_build, nmf as nmf_build, pcm as pcm_build, pitch as pitch_build, ragged as ragged_build, repet as repet_build, repsim as repsim_build, resample as resample_build, tsm as tsm_build  # noqa: F401,E402

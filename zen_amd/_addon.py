@@ -22,7 +22,7 @@ def load(name, symbols):
             if env_var in os.environ:
                 raise ImportError("%s does not exist" % so)
             from . import addon_build
-            addon_build.EVERY_ADDON[name].build()
+            addon_build.EVERY_LIBRARY[name].build()
         _zl.load()                      # the same libzen_hip.so for both bindings (found again beside this one by its rpath)
         L = C.CDLL(so)
         for sym, res, args in symbols:

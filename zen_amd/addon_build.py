@@ -1,13 +1,13 @@
 """Builds the add-on libraries for gfx950 with hipcc: zen_amd/libzen_hip_<name>.so from zen_amd/<name>/, each a library of
 its own on top of libzen_hip.so's C ABI (blockrun: on top of the engine's state as well), and the demo programs zen_amd/bin/pitch-track, zen_amd/bin/beat-track,
-zen_amd/bin/zen-stems, zen_amd/bin/zen-repet, zen_amd/bin/zen-cqt, zen_amd/bin/zen-repsim, zen_amd/bin/zen-nmf and zen_amd/bin/zen-stretch (plain g++: they reach the GPU through two C ABIs only).
+zen_amd/bin/zen-stems, zen_amd/bin/zen-repet, zen_amd/bin/zen-cqt, zen_amd/bin/zen-repsim, zen_amd/bin/zen-nmf, zen_amd/bin/zen-stretch and zen_amd/bin/zen-shift (plain g++: they reach the GPU through C ABIs only).
 
     python zen_amd/addon_build.py [name ...] [--force]         # no name: all of them
 
 Every library links against libzen_hip.so (zen_amd/build.py builds that one first) and finds it beside itself ($ORIGIN).
 -ffp-contract=off and no fast-math flag, for all of them: every float operation of their kernels is a single IEEE operation,
 one rounding each -- the contract of pcm/pcm_convert.h (the division, the products and the rounding are those of the host
-code in zen_amd/cli/wav.h), the one add P1 + R1 of ragged and live, DESIGN.md section 13 for pitch, section 15 for beat, section 17 for repet, section 18 for cqt (whose host tables are part of it), section 19 for repsim, section 20 for nmf and section 21 for tsm (whose host tables are part of it).
+code in zen_amd/cli/wav.h), the one add P1 + R1 of ragged and live, DESIGN.md section 13 for pitch, section 15 for beat, section 17 for repet, section 18 for cqt (whose host tables are part of it), section 19 for repsim, section 20 for nmf, section 21 for tsm and section 22 for resample (whose host tables are part of it).
 """
 import glob
 import os
@@ -75,17 +75,25 @@ class Addon:
         return self.OUT
 
 
-def _build_demo(name, source, exe, verbose):
+def _build_demo(name, source, exe, verbose, extra=()):
     """zen_amd/bin/<exe> from zen_amd/<name>/<source>, against libzen_hip_<name>.so and libzen_hip.so; made again where the
-    source, the library's header, cli/wav.h or the library is newer."""
+    source, the library's header, cli/wav.h or the library is newer.  `extra`: further add-ons whose libraries the program
+    links and whose headers it sees (they are built first where they are absent)."""
     src, out = os.path.join(HERE, name), os.path.join(HERE, "libzen_hip_%s.so" % name)
     srcs = [os.path.join(src, source), os.path.join(src, "zen_hip_%s.h" % name), os.path.join(HERE, "cli", "wav.h"), out]
+    more, libs = [], []
+    for e in extra:
+        if not os.path.exists(EVERY_LIBRARY[e].OUT):
+            EVERY_LIBRARY[e].build(verbose=verbose)
+        srcs += [os.path.join(HERE, e, "zen_hip_%s.h" % e), EVERY_LIBRARY[e].OUT]
+        more += ["-I", os.path.join(HERE, e)]
+        libs.append("-lzen_hip_" + e)
     if os.path.exists(exe) and os.path.getmtime(exe) >= max(os.path.getmtime(p) for p in srcs):
         return exe
     os.makedirs(os.path.dirname(exe), exist_ok=True)
     subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
-                           "-I", src, "-I", os.path.join(HERE, "cli"), srcs[0], "-o", exe, "-L", HERE, "-lzen_hip_" + name, "-lzen_hip",
-                           "-Wl,-rpath,$ORIGIN/.."])
+                           "-I", src, "-I", os.path.join(HERE, "cli")] + more + [srcs[0], "-o", exe, "-L", HERE, "-lzen_hip_" + name] + libs
+                          + ["-lzen_hip", "-Wl,-rpath,$ORIGIN/.."])
     if verbose:
         print("built", exe)
     return exe
@@ -99,6 +107,7 @@ CQT_DEMO = os.path.join(HERE, "bin", "zen-cqt")
 REPSIM_DEMO = os.path.join(HERE, "bin", "zen-repsim")
 NMF_DEMO = os.path.join(HERE, "bin", "zen-nmf")
 STRETCH_DEMO = os.path.join(HERE, "bin", "zen-stretch")
+SHIFT_DEMO = os.path.join(HERE, "bin", "zen-shift")
 
 
 def build_demo(verbose=False):
@@ -131,6 +140,10 @@ def build_nmf_demo(verbose=False):
 
 def build_stretch_demo(verbose=False):
     return _build_demo("tsm", "tsm_main.cpp", STRETCH_DEMO, verbose)
+
+
+def build_shift_demo(verbose=False):
+    return _build_demo("resample", "resample_main.cpp", SHIFT_DEMO, verbose, extra=("tsm",))
 
 
 pcm = Addon("pcm", ["pcm_kernels.hip", "pcm_pipe.hip"], extra_deps=["csrc/host_pipe.h"], title="PCM")
@@ -173,9 +186,15 @@ ALL_ADDONS = {**ADDONS, **ENGINE_ADDONS, **LATER_ADDONS, **FACTOR_ADDONS}
 tsm = Addon("tsm", ["tsm_kernels.hip", "tsm.hip"], build_demo=build_stretch_demo)
 STRETCH_ADDONS = {tsm.name: tsm}
 EVERY_ADDON = {**ALL_ADDONS, **STRETCH_ADDONS}
+# resample (band-limited rate conversion by a rational ratio, and with tsm in front the pitch shift) is on the C ABI alone as
+# well; resample_main.cpp is the demo's, and links tsm's library too.  It has a table of its own again: EVERY_ADDON stays the
+# twelve from before it, and EVERY_LIBRARY is the lookup of the loader and of the command line.
+resample = Addon("resample", ["resample_kernels.hip", "resample.hip"], build_demo=build_shift_demo)
+SHIFT_ADDONS = {resample.name: resample}
+EVERY_LIBRARY = {**EVERY_ADDON, **SHIFT_ADDONS}
 
 
 if __name__ == "__main__":
-    names = [a for a in sys.argv[1:] if not a.startswith("--")] or list(EVERY_ADDON)
+    names = [a for a in sys.argv[1:] if not a.startswith("--")] or list(EVERY_LIBRARY)
     for n in names:
-        EVERY_ADDON[n].build(force="--force" in sys.argv, verbose=True)
+        EVERY_LIBRARY[n].build(force="--force" in sys.argv, verbose=True)
