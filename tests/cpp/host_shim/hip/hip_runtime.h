@@ -11,6 +11,10 @@ struct float2 {
 	float x, y;
 };
 static inline float2 make_float2(float x, float y) { return {x, y}; }
+struct alignas(16) float4 { // zen_amd/addon/median_select.h (tests/cpp/test_addon_median_host.cpp)
+	float x, y, z, w;
+};
+static inline float4 make_float4(float x, float y, float z, float w) { return {x, y, z, w}; }
 // (named by functions of fft_dev.h the host test never calls)
 #define __builtin_amdgcn_fence(order, scope) ((void)0)
 #define __builtin_amdgcn_wave_barrier() ((void)0)

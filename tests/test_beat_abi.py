@@ -142,7 +142,7 @@ def test_build_keeps_the_arithmetic_contract_and_the_engines_apart():
         assert "csrc/" not in re.sub(r"//.*", "", text), name
         for inc in re.findall(r'#include "([^"]+)"', text):
             assert inc in ("zen_hip.h", "zen_hip_beat.h", "beat_kernels.h", "beat_tables.h", "wav.h", "../addon/addon_host.h"), (name, inc)
-    assert sorted(os.listdir(os.path.join(ROOT, "zen_amd", "addon"))) == ["addon_host.h", "hpri_pair.h", "row_walk.h"]
+    assert sorted(os.listdir(os.path.join(ROOT, "zen_amd", "addon"))) == ["addon_host.h", "hpri_pair.h", "median_select.h", "row_walk.h", "stft_args.h", "stft_host.h", "stft_kernels.h"]
 
 
 def test_demo_program_is_built_and_states_its_usage(beat_so):

@@ -214,6 +214,20 @@ def test_median_networks_on_the_host(tmp_path):
     assert r.returncode == 0 and "passed" in r.stdout, r.stdout[-2000:]
 
 
+def test_addon_median_selection_on_the_host(tmp_path):
+    """zen_amd/addon/median_select.h compiled as plain C++ behind tests/cpp/host_shim (tests/cpp/test_addon_median_host.cpp),
+    with the address and undefined-behaviour sanitizers: the bitonic networks of 2..32 values at every count 1..P (random
+    values, all equal, +-0 mixed, denormals, +inf among the values) against std::sort and the (lo + hi) * 0.5f rule, and the
+    register-median body zen_amd/repet and repsim share on a 3 x 9 matrix, one bin and four bins per lane, for rows a stride
+    apart and rows an index list names."""
+    exe = str(tmp_path / "test_addon_median_host")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(ROOT, "tests", "cpp", "host_shim"), os.path.join(ROOT, "tests", "cpp", "test_addon_median_host.cpp"),
+                           "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "passed" in r.stdout and not r.stderr, (r.stdout[-2000:], r.stderr[-2000:])
+
+
 def test_block_merge_selection_on_the_host(tmp_path):
     """zen_amd/csrc/median_big.h compiled as plain C++ (tests/cpp/test_median_big_host.cpp): zbig::medians_big<W> for every long
     mask the kernels instantiate (65 .. 257 taps), through a loader of sorted 16-blocks and through one that also hands out

@@ -141,7 +141,7 @@ def test_sources_see_the_listed_headers_only_and_nothing_of_the_engines():
     assert '#include "../pcm/pcm_convert.h"' in kernels and "32767" not in kernels
     for fn in ("pcm16_to_float", "float_to_pcm16_gain", "float_to_pcm16_peak", "pcm16_peak_of"):
         assert fn in kernels, fn
-    assert sorted(os.listdir(os.path.join(ROOT, "zen_amd", "addon"))) == ["addon_host.h", "hpri_pair.h", "row_walk.h"]
+    assert sorted(os.listdir(os.path.join(ROOT, "zen_amd", "addon"))) == ["addon_host.h", "hpri_pair.h", "median_select.h", "row_walk.h", "stft_args.h", "stft_host.h", "stft_kernels.h"]
 
 
 def test_wav_writer_keeps_the_channels(tmp_path):

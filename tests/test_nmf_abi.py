@@ -202,9 +202,10 @@ def test_build_keeps_the_arithmetic_contract_and_the_other_libraries_apart():
         assert "csrc/" not in re.sub(r"//.*", "", text), name
         assert "asm" not in re.sub(r"//.*", "", text).split(), name
         for inc in re.findall(r'#include "([^"]+)"', text):
-            assert inc in ("zen_hip.h", "zen_hip_nmf.h", "nmf_kernels.h", "wav.h", "../addon/addon_host.h"), (name, inc)
+            assert inc in ("zen_hip.h", "zen_hip_nmf.h", "nmf_kernels.h", "wav.h", "../addon/addon_host.h", "../addon/stft_host.h", "../addon/stft_args.h",
+                           "../addon/stft_kernels.h"), (name, inc)
     zen = os.path.join(ROOT, "zen_amd")
-    assert sorted(os.listdir(os.path.join(zen, "addon"))) == ["addon_host.h", "hpri_pair.h", "row_walk.h"]
+    assert sorted(os.listdir(os.path.join(zen, "addon"))) == ["addon_host.h", "hpri_pair.h", "median_select.h", "row_walk.h", "stft_args.h", "stft_host.h", "stft_kernels.h"]
     assert sorted(os.listdir(os.path.join(zen, "repet"))) == ["repet.hip", "repet_kernels.h", "repet_kernels.hip", "repet_main.cpp", "zen_hip_repet.h"]
     assert sorted(os.listdir(os.path.join(zen, "repsim"))) == ["repsim.hip", "repsim_kernels.h", "repsim_kernels.hip", "repsim_main.cpp",
                                                                "zen_hip_repsim.h"]

@@ -165,8 +165,9 @@ def test_build_keeps_the_arithmetic_contract_and_the_other_libraries_apart():
         text = open(os.path.join(addon.SRC, name)).read()
         assert "csrc/" not in re.sub(r"//.*", "", text) and "median_net.h" not in text, name
         for inc in re.findall(r'#include "([^"]+)"', text):
-            assert inc in ("zen_hip.h", "zen_hip_repsim.h", "repsim_kernels.h", "wav.h", "../addon/addon_host.h"), (name, inc)
-    assert sorted(os.listdir(os.path.join(ROOT, "zen_amd", "addon"))) == ["addon_host.h", "hpri_pair.h", "row_walk.h"]
+            assert inc in ("zen_hip.h", "zen_hip_repsim.h", "repsim_kernels.h", "wav.h", "../addon/addon_host.h", "../addon/stft_host.h", "../addon/stft_args.h",
+                           "../addon/stft_kernels.h", "../addon/median_select.h"), (name, inc)
+    assert sorted(os.listdir(os.path.join(ROOT, "zen_amd", "addon"))) == ["addon_host.h", "hpri_pair.h", "median_select.h", "row_walk.h", "stft_args.h", "stft_host.h", "stft_kernels.h"]
     assert sorted(os.listdir(os.path.join(ROOT, "zen_amd", "repet"))) == ["repet.hip", "repet_kernels.h", "repet_kernels.hip", "repet_main.cpp",
                                                                           "zen_hip_repet.h"]
 

@@ -1,6 +1,7 @@
-// addon_host.h -- what the host sources of the add-on libraries share (zen_amd/pcm, ragged, live, pitch: each a library of
-// its own on top of libzen_hip.so's C ABI, include/zen_hip.h): the thread's error message and the macros that set it, the
-// per-kernel profile, the counting allocator and the roll-back of a create function.
+// addon_host.h -- what the host sources of the add-on libraries share (zen_amd/pcm, ragged, live, pitch and every add-on
+// since: each a library of its own on top of libzen_hip.so's C ABI, include/zen_hip.h): the thread's error message and the
+// macros that set it, the per-kernel profile, the counting allocator and the roll-back of a create function.  What the
+// spectrogram add-ons share beyond that is stft_host.h and, on the device side, stft_kernels.h and median_select.h.
 //
 // Header-only, and everything in it has internal linkage (the anonymous namespace): the libraries are routinely loaded into
 // one process, and a symbol of default visibility would be resolved to whichever of them was loaded first -- one library's

@@ -19,7 +19,7 @@
 
 #include "zen_hip_nmf.h"
 
-#include "../addon/addon_host.h"
+#include "../addon/stft_host.h"
 #include "nmf_kernels.h"
 
 using namespace zen_addon;
@@ -35,13 +35,6 @@ static_assert((int)zen_nmf::MAX_COMPONENTS == ZEN_HIP_NMF_MAX_COMPONENTS && (int
 constexpr size_t KMAX = ZEN_HIP_NMF_MAX_COMPONENTS, MMAX = ZEN_HIP_NMF_MAX_FRAMES;
 // The route of ZEN_HIP_NMF_ROUTE_DEFAULT.
 constexpr bool DEFAULT_MFMA = true;
-
-bool is_pow2(size_t v) { return v && !(v & (v - 1)); }
-bool frame_ok(size_t nfft) { return is_pow2(nfft) && nfft >= 64 && nfft <= 8192; }
-size_t frames_of(size_t n, size_t H) { return (n + H - 1) / H + 1; }
-float window_at(size_t i, size_t N) { return (float)(0.54 - 0.46 * cos(2.0 * M_PI * (double)i / (double)N)); }
-float divisor_at(size_t i, size_t N) { return (float)((double)N * ((double)window_at(i, N) + (double)window_at(i + N / 2, N))); }
-bool misaligned(const void* p) { return ((uintptr_t)p & 3) != 0; }
 
 } // namespace
 
@@ -78,28 +71,8 @@ int alloc(zen_hip_nmf* h, T** p, size_t count)
 // steps 1-2 for every clip
 int spectra(zen_hip_nmf* h, const float* in, size_t in_stride, size_t n, size_t m)
 {
-	const size_t N = h->N, frames = h->C * m;
-	{
-		zen_nmf::FrameArgs a = {in, h->tables, h->rows, in_stride, n, m, h->C, (int)N};
-		auto kt = h->prof.on_stream(h->stream);
-		ZA_TRY(kt.begin(K_FRAME, sizeof(float) * (h->C * n + frames * 2 * N)));
-		ZA_HIP(zen_nmf::launch_frame(a, h->stream));
-		ZA_TRY(kt.end());
-	}
-	{
-		auto kt = h->prof.on_stream(h->stream);
-		ZA_TRY(kt.begin(K_FFT, sizeof(float) * frames * 4 * N));
-		ZA_ZEN(zen_hip_fft_exec_batched(h->fft, h->rows, frames, 0, h->stream));
-		ZA_TRY(kt.end());
-	}
-	{
-		zen_nmf::MagArgs a = {h->rows, h->v, h->v_stride, frames, (int)N};
-		auto kt = h->prof.on_stream(h->stream);
-		ZA_TRY(kt.begin(K_MAG, sizeof(float) * frames * (2 * h->bins + h->v_stride)));
-		ZA_HIP(zen_nmf::launch_magnitude(a, h->stream));
-		ZA_TRY(kt.end());
-	}
-	return ZEN_HIP_OK;
+	const FrameArgs a = {in, h->tables, h->rows, in_stride, n, m, h->C, (int)h->N};
+	return zen_addon::spectra(h->prof, h->stream, h->fft, K_FRAME, K_FFT, K_MAG, zen_nmf::launch_frame, zen_nmf::launch_magnitude, a, h->v, h->v_stride);
 }
 
 struct Matrices { // one clip's W and H as the caller laid them out
@@ -284,11 +257,7 @@ int zen_hip_nmf_create(float fs, size_t nfft, size_t components, size_t n_clips,
 		h->mfma = true;
 	auto build = [&]() -> int {
 		const size_t frames = n_clips * h->max_frames;
-		std::vector<float> tab(nfft + H);
-		for (size_t i = 0; i < nfft; ++i)
-			tab[i] = window_at(i, nfft);
-		for (size_t i = 0; i < H; ++i)
-			tab[nfft + i] = divisor_at(i, nfft);
+		const std::vector<float> tab = stft_tables(nfft);
 		ZA_ZEN(zen_hip_fft_create(nfft, &h->fft));
 		ZA_TRY(alloc(h, &h->rows, frames * 2 * nfft));
 		ZA_TRY(alloc(h, &h->masked, h->max_frames * 2 * nfft));

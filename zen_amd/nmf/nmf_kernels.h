@@ -7,26 +7,16 @@
 
 #include <stddef.h>
 
+#include "../addon/stft_args.h"
+
 namespace zen_nmf {
 
 enum { MAX_COMPONENTS = 256, MAX_FRAMES = 16384, SEGMENT = 256 };
 enum { TILE = 128 }; // rows and columns of a product per workgroup
 enum Product { RATIO = 0, UPDATE_H = 1, UPDATE_W = 2 };
 
-struct FrameArgs {
-	const float* in;  // clip c: in + c * in_stride, n samples
-	const float* win; // N floats
-	float* rows;      // n_clips * m rows of N complex values
-	size_t in_stride, n, m, n_clips;
-	int N;
-};
-
-struct MagArgs {
-	const float* rows;
-	float* v; // rows of v_stride floats; the floats behind bin H are written as +0
-	size_t v_stride, frames; // frames = n_clips * m
-	int N;
-};
+using zen_addon::FrameArgs; // ../addon/stft_args.h, with the layout of a call's rows
+using zen_addon::MagArgs;
 
 // out[i][j] = epilogue(sdot over l < L of (A(i, l), B(l, j))), i < I, j < J.  An operand is reduction-minor (A(i, l) =
 // a[i * a_stride + l]) or reduction-major (A(i, l) = a[l * a_stride + i]) as its product has it:
@@ -69,8 +59,10 @@ struct OlaArgs { // one clip
 	int N;
 };
 
-hipError_t launch_frame(const FrameArgs& a, hipStream_t s);
-hipError_t launch_magnitude(const MagArgs& a, hipStream_t s);
+// the first two are ../addon/stft_kernels.h's as this library compiled them; hidden: their names spell a type of zen_addon,
+// and nothing of zen_amd/addon is among a library's dynamic symbols
+__attribute__((visibility("hidden"))) hipError_t launch_frame(const FrameArgs& a, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_magnitude(const MagArgs& a, hipStream_t s);
 hipError_t launch_product(Product which, const ProductArgs& a, bool mfma, hipStream_t s); // the segments in sequence
 hipError_t launch_product_split(Product which, const ProductArgs& a, bool mfma, hipStream_t s); // UPDATE_H / UPDATE_W: partial sums, then combine
 hipError_t launch_stem_mask(const StemArgs& a, hipStream_t s);

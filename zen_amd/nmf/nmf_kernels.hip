@@ -8,12 +8,14 @@
 // contract fixes is an fma chain in that order on both routes: v_mfma_f32_32x32x2_f32 adds its two products in k order with
 // one rounding each, the reduction loop feeds it the indices in rising order, and at every 256th index the accumulators are
 // added to the running totals (the first is taken as it is) and start again from +0 -- the segments of the contract.  frame,
-// magnitude and overlap_add are zen_amd/repet's, copied: that library's files are pinned, and zen_amd/addon holds no kernels.
+// magnitude, the sample of overlap_add and the loader of a reduction-minor LDS tile are zen_amd/addon/stft_kernels.h's: shared
+// with zen_amd/repet and repsim.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <stdint.h>
 
+#include "../addon/stft_kernels.h"
 #include "nmf_kernels.h"
 
 #pragma clang fp contract(off)
@@ -21,44 +23,9 @@
 namespace zen_nmf {
 namespace {
 
-constexpr int TPB = 256;
+using namespace zen_addon;
+
 constexpr float EPS = 0x1p-40f;
-
-unsigned clip_rows(size_t n_clips) { return (unsigned)(n_clips < 65535 ? n_clips : 65535); }
-
-// ------------------------------------------------------------------------------------------------ frame
-// xp is H zeros, the clip, zeros: sample j of frame k is x[k H - H + j]
-__global__ __launch_bounds__(TPB) void frame_kernel(FrameArgs k)
-{
-	const int N = k.N, H = N / 2;
-	const size_t f = blockIdx.x;
-	for (size_t c = blockIdx.y; c < k.n_clips; c += gridDim.y) {
-		const float* __restrict__ x = k.in + c * k.in_stride;
-		float2* __restrict__ row = reinterpret_cast<float2*>(k.rows) + (c * k.m + f) * (size_t)N;
-		for (int j = threadIdx.x; j < N; j += TPB) {
-			const size_t pos = f * (size_t)H + (size_t)j; // index into xp
-			const float v = pos >= (size_t)H && pos - H < k.n ? x[pos - H] : 0.0f;
-			row[j] = make_float2(v * k.win[j], 0.0f);
-		}
-	}
-}
-
-// ------------------------------------------------------------------------------------------------ magnitude
-__global__ __launch_bounds__(TPB) void magnitude_kernel(MagArgs k)
-{
-	const int N = k.N, H = N / 2;
-	const size_t f = blockIdx.x;
-	const float2* __restrict__ row = reinterpret_cast<const float2*>(k.rows) + f * (size_t)N;
-	float* __restrict__ v = k.v + f * k.v_stride;
-	for (size_t i = threadIdx.x; i < k.v_stride; i += TPB) {
-		float r = 0.0f;
-		if (i <= (size_t)H) {
-			const float2 z = row[i];
-			r = sqrtf(z.x * z.x + z.y * z.y);
-		}
-		v[i] = r;
-	}
-}
 
 // ------------------------------------------------------------------------------------------------ product
 // A workgroup of four waves computes a TILE x TILE block of a product: wave w the 64 x 64 quadrant (w >> 1, w & 1) as 2 x 2
@@ -75,47 +42,9 @@ __global__ __launch_bounds__(TPB) void magnitude_kernel(MagArgs k)
 // sums over the A operand's rows along the same reduction with the same segments: one thread per row of the block carries
 // fma(A, 1, acc) beside the products, 1/128 of the block's work, and no launch or scratch of their own.  x + (-0) is x, so
 // the padding leaves them alone as well.
-constexpr int KC = 32;
-constexpr int LDK = KC + 1;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// T[r * LDK + q] = v[(r0 + r) * stride + l0 + q]: rows r0.. of a reduction-minor operand
-template <bool VEC>
-__device__ __forceinline__ void load_minor(float* __restrict__ T, const float* __restrict__ v, size_t stride, size_t r0, size_t rows, size_t l0,
-                                           size_t L, float pad, int tid)
-{
-	if (VEC) { // v 16-byte aligned, stride a multiple of 4
-#pragma unroll
-		for (int i = 0; i < TILE * KC / 4 / TPB; ++i) {
-			const int s = tid + TPB * i, r = s >> 3, q = (s & 7) * 4;
-			const size_t row = r0 + r, l = l0 + q;
-			float4 x = make_float4(pad, pad, pad, pad);
-			if (row < rows) {
-				const float* __restrict__ p = v + row * stride + l;
-				if (l + 4 <= L) {
-					x = *reinterpret_cast<const float4*>(p);
-				} else {
-					x.x = l < L ? p[0] : pad;
-					x.y = l + 1 < L ? p[1] : pad;
-					x.z = l + 2 < L ? p[2] : pad;
-				}
-			}
-			float* __restrict__ d = T + r * LDK + q;
-			d[0] = x.x;
-			d[1] = x.y;
-			d[2] = x.z;
-			d[3] = x.w;
-		}
-	} else {
-#pragma unroll
-		for (int i = 0; i < TILE * KC / TPB; ++i) {
-			const int e = tid + TPB * i, r = e >> 5, q = e & 31;
-			const size_t row = r0 + r, l = l0 + q;
-			T[r * LDK + q] = row < rows && l < L ? v[row * stride + l] : pad;
-		}
-	}
-}
-
+// Rows r0.. of a reduction-minor operand go through stft_kernels.h's load_tile.  The other one, with the same arguments:
 // T[r * LDK + q] = v[(l0 + q) * stride + r0 + r]: columns r0.. of a reduction-major operand
 template <bool VEC>
 __device__ __forceinline__ void load_major(float* __restrict__ T, const float* __restrict__ v, size_t stride, size_t r0, size_t rows, size_t l0,
@@ -184,11 +113,11 @@ __global__ __launch_bounds__(TPB) void product_kernel(ProductArgs k)
 		if (A_MAJOR)
 			load_major<VEC>(As, k.a, k.a_stride, i0, k.I, l0, k.L, -0.0f, tid);
 		else
-			load_minor<VEC>(As, k.a, k.a_stride, i0, k.I, l0, k.L, -0.0f, tid);
+			load_tile<TILE, VEC>(As, k.a, k.a_stride, i0, k.I, l0, k.L, -0.0f, tid);
 		if (B_MAJOR)
 			load_major<VEC>(Bs, k.b, k.b_stride, j0, k.J, l0, k.L, 0.0f, tid);
 		else
-			load_minor<VEC>(Bs, k.b, k.b_stride, j0, k.J, l0, k.L, 0.0f, tid);
+			load_tile<TILE, VEC>(Bs, k.b, k.b_stride, j0, k.J, l0, k.L, 0.0f, tid);
 		__syncthreads();
 		if (SEG) {
 #pragma unroll
@@ -355,17 +284,11 @@ __global__ __launch_bounds__(TPB) void stem_mask_kernel(StemArgs k)
 // ------------------------------------------------------------------------------------------------ overlap-add
 __global__ __launch_bounds__(TPB) void overlap_add_kernel(OlaArgs k)
 {
-	const int N = k.N, H = N / 2;
 	const size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
 	if (t >= k.n)
 		return;
-	const size_t fr = t / H;
-	const int i = (int)(t % H);
-	const float2* __restrict__ g = reinterpret_cast<const float2*>(k.rows);
-	k.out[t] = (g[fr * N + H + i].x + g[(fr + 1) * N + i].x) / k.div[i]; // the earlier frame first
+	k.out[t] = overlap_add_sample(k.rows, k.div, t, k.N);
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 template <int WHICH, bool PART>
 hipError_t launch_one(const ProductArgs& a, bool mfma, hipStream_t s)
@@ -395,21 +318,8 @@ bool product_ok(Product which, const ProductArgs& a)
 
 } // namespace
 
-hipError_t launch_frame(const FrameArgs& a, hipStream_t s)
-{
-	if (a.m == 0 || a.n_clips == 0)
-		return hipSuccess;
-	frame_kernel<<<dim3((unsigned)a.m, clip_rows(a.n_clips), 1), TPB, 0, s>>>(a);
-	return hipGetLastError();
-}
-
-hipError_t launch_magnitude(const MagArgs& a, hipStream_t s)
-{
-	if (a.frames == 0)
-		return hipSuccess;
-	magnitude_kernel<<<dim3((unsigned)a.frames, 1, 1), TPB, 0, s>>>(a);
-	return hipGetLastError();
-}
+hipError_t launch_frame(const FrameArgs& a, hipStream_t s) { return zen_addon::launch_frame(a, s); }
+hipError_t launch_magnitude(const MagArgs& a, hipStream_t s) { return zen_addon::launch_magnitude(a, s); }
 
 hipError_t launch_product(Product which, const ProductArgs& a, bool mfma, hipStream_t s)
 {

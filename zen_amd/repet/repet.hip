@@ -16,7 +16,7 @@
 
 #include "zen_hip_repet.h"
 
-#include "../addon/addon_host.h"
+#include "../addon/stft_host.h"
 #include "repet_kernels.h"
 
 using namespace zen_addon;
@@ -30,9 +30,6 @@ static_assert((int)zen_repet::MAX_SEGMENTS == ZEN_HIP_REPET_MAX_SEGMENTS && (int
 
 constexpr size_t MIN_LAG = 64;
 
-bool is_pow2(size_t v) { return v && !(v & (v - 1)); }
-bool frame_ok(size_t nfft) { return is_pow2(nfft) && nfft >= 64 && nfft <= 8192; }
-size_t frames_of(size_t n, size_t H) { return (n + H - 1) / H + 1; }
 size_t lag_points(size_t m)
 {
 	size_t L = MIN_LAG;
@@ -40,8 +37,6 @@ size_t lag_points(size_t m)
 		L *= 2;
 	return L;
 }
-float window_at(size_t i, size_t N) { return (float)(0.54 - 0.46 * cos(2.0 * M_PI * (double)i / (double)N)); }
-float divisor_at(size_t i, size_t N) { return (float)((double)N * ((double)window_at(i, N) + (double)window_at(i + N / 2, N))); }
 
 } // namespace
 
@@ -86,28 +81,8 @@ zen_hip_fft_t lag_handle(const zen_hip_repet* h, size_t L)
 // steps 1-2 for every clip
 int spectra(zen_hip_repet* h, const float* in, size_t in_stride, size_t n, size_t m)
 {
-	const size_t N = h->N, frames = h->C * m;
-	{
-		zen_repet::FrameArgs a = {in, h->tables, h->rows, in_stride, n, m, h->C, (int)N};
-		auto kt = h->prof.on_stream(h->stream);
-		ZA_TRY(kt.begin(K_FRAME, sizeof(float) * (h->C * n + frames * 2 * N)));
-		ZA_HIP(zen_repet::launch_frame(a, h->stream));
-		ZA_TRY(kt.end());
-	}
-	{
-		auto kt = h->prof.on_stream(h->stream);
-		ZA_TRY(kt.begin(K_FFT, sizeof(float) * frames * 4 * N));
-		ZA_ZEN(zen_hip_fft_exec_batched(h->fft, h->rows, frames, 0, h->stream));
-		ZA_TRY(kt.end());
-	}
-	{
-		zen_repet::MagArgs a = {h->rows, h->v, h->v_stride, frames, (int)N};
-		auto kt = h->prof.on_stream(h->stream);
-		ZA_TRY(kt.begin(K_MAG, sizeof(float) * frames * (2 * h->bins + h->v_stride)));
-		ZA_HIP(zen_repet::launch_magnitude(a, h->stream));
-		ZA_TRY(kt.end());
-	}
-	return ZEN_HIP_OK;
+	const FrameArgs a = {in, h->tables, h->rows, in_stride, n, m, h->C, (int)h->N};
+	return zen_addon::spectra(h->prof, h->stream, h->fft, K_FRAME, K_FFT, K_MAG, zen_repet::launch_frame, zen_repet::launch_magnitude, a, h->v, h->v_stride);
 }
 
 // step 3 for clip c: braw_row receives m floats in device memory
@@ -319,11 +294,7 @@ int zen_hip_repet_create(float fs, size_t nfft, size_t n_clips, size_t max_sampl
 	h->max_lag = lag_points(h->max_frames);
 	auto build = [&]() -> int {
 		const size_t frames = n_clips * h->max_frames;
-		std::vector<float> tab(nfft + H);
-		for (size_t i = 0; i < nfft; ++i)
-			tab[i] = window_at(i, nfft);
-		for (size_t i = 0; i < H; ++i)
-			tab[nfft + i] = divisor_at(i, nfft);
+		const std::vector<float> tab = stft_tables(nfft);
 		h->braw_host.assign(frames, 0.0f);
 		h->period.assign(n_clips, 0);
 		ZA_ZEN(zen_hip_fft_create(nfft, &h->fft));

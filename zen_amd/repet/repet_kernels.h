@@ -7,24 +7,14 @@
 
 #include <stddef.h>
 
+#include "../addon/stft_args.h"
+
 namespace zen_repet {
 
 enum { MAX_SEGMENTS = 256, REGISTER_SEGMENTS = 32 }; // counts up to REGISTER_SEGMENTS are sorted in registers, the rest in LDS
 
-struct FrameArgs {
-	const float* in;  // clip c: in + c * in_stride, n samples
-	const float* win; // N floats
-	float* rows;      // n_clips * m rows of N complex values
-	size_t in_stride, n, m, n_clips;
-	int N;
-};
-
-struct MagArgs {
-	const float* rows;
-	float* v; // rows of v_stride floats; the floats behind bin H are written as +0
-	size_t v_stride, frames; // frames = n_clips * m
-	int N;
-};
+using zen_addon::FrameArgs; // ../addon/stft_args.h, with the layout of a call's rows
+using zen_addon::MagArgs;
 
 struct LagArgs { // one clip: V (m rows) -> bins rows of L complex values (V^2, 0), zeros from m on
 	const float* v;
@@ -68,8 +58,10 @@ struct OlaArgs { // one clip
 	int N;
 };
 
-hipError_t launch_frame(const FrameArgs& a, hipStream_t s);
-hipError_t launch_magnitude(const MagArgs& a, hipStream_t s);
+// the first two are ../addon/stft_kernels.h's as this library compiled them; hidden: their names spell a type of zen_addon,
+// and nothing of zen_amd/addon is among a library's dynamic symbols
+__attribute__((visibility("hidden"))) hipError_t launch_frame(const FrameArgs& a, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_magnitude(const MagArgs& a, hipStream_t s);
 hipError_t launch_lag_rows(const LagArgs& a, hipStream_t s);
 hipError_t launch_power(const PowerArgs& a, hipStream_t s);
 hipError_t launch_braw(const BrawArgs& a, hipStream_t s);

@@ -7,12 +7,15 @@
 // off, hipcc's correctly rounded division and square root): tests/repet_model.py gives the same bits.  The one sum whose
 // order the contract fixes (braw, over the bins) is added by one thread in that order.  A median is a selection: it is exact
 // however it is found, so the two paths of segment_median (a sorting network in registers, a sort of lane-private columns in
-// LDS) give the same values.
+// LDS) give the same values.  frame, magnitude, the body of mask and the sample of overlap_add are zen_amd/addon/stft_kernels.h's,
+// the sorting network and the pick of the median zen_amd/addon/median_select.h's: shared with zen_amd/repsim and nmf.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <stdint.h>
 
+#include "../addon/median_select.h"
+#include "../addon/stft_kernels.h"
 #include "repet_kernels.h"
 
 #pragma clang fp contract(off)
@@ -20,44 +23,9 @@
 namespace zen_repet {
 namespace {
 
-constexpr int TPB = 256;
+using namespace zen_addon;
+
 constexpr int TILE = 64; // lag_rows: frames x bins per workgroup
-
-unsigned clip_rows(size_t n_clips) { return (unsigned)(n_clips < 65535 ? n_clips : 65535); }
-
-// ------------------------------------------------------------------------------------------------ frame
-// xp is H zeros, the clip, zeros: sample j of frame k is x[k H - H + j]
-__global__ __launch_bounds__(TPB) void frame_kernel(FrameArgs k)
-{
-	const int N = k.N, H = N / 2;
-	const size_t f = blockIdx.x;
-	for (size_t c = blockIdx.y; c < k.n_clips; c += gridDim.y) {
-		const float* __restrict__ x = k.in + c * k.in_stride;
-		float2* __restrict__ row = reinterpret_cast<float2*>(k.rows) + (c * k.m + f) * (size_t)N;
-		for (int j = threadIdx.x; j < N; j += TPB) {
-			const size_t pos = f * (size_t)H + (size_t)j; // index into xp
-			const float v = pos >= (size_t)H && pos - H < k.n ? x[pos - H] : 0.0f;
-			row[j] = make_float2(v * k.win[j], 0.0f);
-		}
-	}
-}
-
-// ------------------------------------------------------------------------------------------------ magnitude
-__global__ __launch_bounds__(TPB) void magnitude_kernel(MagArgs k)
-{
-	const int N = k.N, H = N / 2;
-	const size_t f = blockIdx.x;
-	const float2* __restrict__ row = reinterpret_cast<const float2*>(k.rows) + f * (size_t)N;
-	float* __restrict__ v = k.v + f * k.v_stride;
-	for (size_t i = threadIdx.x; i < k.v_stride; i += TPB) {
-		float r = 0.0f;
-		if (i <= (size_t)H) {
-			const float2 z = row[i];
-			r = sqrtf(z.x * z.x + z.y * z.y);
-		}
-		v[i] = r;
-	}
-}
 
 // ------------------------------------------------------------------------------------------------ lag rows
 // A tile of TILE frames x TILE bins: read along the bins, written along the frames, through LDS (a row of TILE + 1 words
@@ -109,51 +77,12 @@ __global__ __launch_bounds__(TPB) void braw_kernel(BrawArgs k)
 }
 
 // ------------------------------------------------------------------------------------------------ segment median
-__device__ __forceinline__ void cswap(float& a, float& b) // a permutation of (a, b) for every pair of non-NaN values
-{
-	const bool gt = a > b;
-	const float lo = gt ? b : a, hi = gt ? a : b;
-	a = lo;
-	b = hi;
-}
-
-template <int P>
-__device__ __forceinline__ void sort_network(float (&a)[P]) // the bitonic network on P values, ascending
-{
-#pragma unroll
-	for (int k = 2; k <= P; k <<= 1) {
-#pragma unroll
-		for (int j = k >> 1; j > 0; j >>= 1) {
-#pragma unroll
-			for (int i = 0; i < P; ++i) {
-				const int l = i ^ j;
-				if (l > i) {
-					if ((i & k) == 0)
-						cswap(a[i], a[l]);
-					else
-						cswap(a[l], a[i]);
-				}
-			}
-		}
-	}
-}
-
-template <int P>
-__device__ __forceinline__ float pick_median(const float (&a)[P], int c) // c values sorted in front of P - c times +inf
-{
-	const int lo = (c - 1) >> 1, hi = c >> 1;
-	float slo = a[0], shi = a[0];
-#pragma unroll
-	for (int i = 1; i < P; ++i) { // every index is a constant: the values stay in registers
-		slo = i == lo ? a[i] : slo;
-		shi = i == hi ? a[i] : shi;
-	}
-	return (c & 1) ? slo : (slo + shi) * 0.5f;
-}
-
 // counts up to P in registers.  A lane has VEC adjacent bins of one row l of the segment: every sweep q is a coalesced row
 // read (16 bytes per lane for VEC = 4) and the VEC networks are independent of each other.  VEC = 4 wants v and s 16-byte
 // aligned and both strides multiples of 4; the lanes at the end of a row fall back to single words.
+// The loop is this kernel's own and not median_select.h's median_in_registers, which zen_amd/repsim's gathered rows go
+// through: through that body the 32-row kernel took 163 registers for 138 and 0.0222 ms for 0.0200 ms on 7753 frames of 1025
+// bins (profiles/stft_shared_ab.json).
 template <int P, int VEC>
 __global__ __launch_bounds__(TPB) void median_reg_kernel(MedianArgs k)
 {
@@ -249,40 +178,22 @@ hipError_t launch_reg(const MedianArgs& a, bool vec, hipStream_t s)
 // ------------------------------------------------------------------------------------------------ mask
 __global__ __launch_bounds__(TPB) void mask_kernel(MaskArgs k)
 {
-	const int N = k.N, H = N / 2;
 	const size_t fr = blockIdx.x;
-	float2* __restrict__ row = reinterpret_cast<float2*>(k.rows) + fr * (size_t)N;
-	const float* __restrict__ v = k.v + fr * k.v_stride;
-	const float* __restrict__ s = k.s + (fr % k.period) * k.v_stride;
-	for (int f = threadIdx.x; f <= H; f += TPB) {
-		const float V = v[f], S = s[f];
-		const float W = S < V ? S : V;
-		float M = V > 0.0f ? W / V : 0.0f;
-		if (f < k.kc)
-			M = 1.0f;
-		const float2 z = row[f];
-		row[f] = make_float2(z.x * M, z.y * M);
-		if (f > 0 && f < H) {
-			const float2 y = row[N - f];
-			row[N - f] = make_float2(y.x * M, y.y * M);
-		}
-	}
+	float2* __restrict__ row = reinterpret_cast<float2*>(k.rows) + fr * (size_t)k.N;
+	const float* __restrict__ s = k.s + (fr % k.period) * k.v_stride; // the model of a frame is its row of the segment
+	soft_mask_frame(row, k.v + fr * k.v_stride, s, k.N, k.kc);
 }
 
 // ------------------------------------------------------------------------------------------------ overlap-add
 __global__ __launch_bounds__(TPB) void overlap_add_kernel(OlaArgs k)
 {
-	const int N = k.N, H = N / 2;
 	const size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
 	if (t >= k.n)
 		return;
 	const float x = k.in[t];
 	float bg = 0.0f, fg = x;
 	if (k.period) {
-		const size_t fr = t / H;
-		const int i = (int)(t % H);
-		const float2* __restrict__ g = reinterpret_cast<const float2*>(k.rows);
-		bg = (g[fr * N + H + i].x + g[(fr + 1) * N + i].x) / k.div[i]; // the earlier frame first
+		bg = overlap_add_sample(k.rows, k.div, t, k.N);
 		fg = x - bg;
 	}
 	if (k.background)
@@ -293,21 +204,8 @@ __global__ __launch_bounds__(TPB) void overlap_add_kernel(OlaArgs k)
 
 } // namespace
 
-hipError_t launch_frame(const FrameArgs& a, hipStream_t s)
-{
-	if (a.m == 0 || a.n_clips == 0)
-		return hipSuccess;
-	frame_kernel<<<dim3((unsigned)a.m, clip_rows(a.n_clips), 1), TPB, 0, s>>>(a);
-	return hipGetLastError();
-}
-
-hipError_t launch_magnitude(const MagArgs& a, hipStream_t s)
-{
-	if (a.frames == 0)
-		return hipSuccess;
-	magnitude_kernel<<<dim3((unsigned)a.frames, 1, 1), TPB, 0, s>>>(a);
-	return hipGetLastError();
-}
+hipError_t launch_frame(const FrameArgs& a, hipStream_t s) { return zen_addon::launch_frame(a, s); }
+hipError_t launch_magnitude(const MagArgs& a, hipStream_t s) { return zen_addon::launch_magnitude(a, s); }
 
 hipError_t launch_lag_rows(const LagArgs& a, hipStream_t s)
 {

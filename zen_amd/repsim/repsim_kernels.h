@@ -7,25 +7,15 @@
 
 #include <stddef.h>
 
+#include "../addon/stft_args.h"
+
 namespace zen_repsim {
 
 enum { MAX_NEIGHBOURS = 256, REGISTER_NEIGHBOURS = 32, MAX_FRAMES = 16384 }; // counts up to REGISTER_NEIGHBOURS are sorted in registers
 enum { SIM_TILE = 128 }; // similarity: rows and columns of S per workgroup
 
-struct FrameArgs {
-	const float* in;  // clip c: in + c * in_stride, n samples
-	const float* win; // N floats
-	float* rows;      // n_clips * m rows of N complex values
-	size_t in_stride, n, m, n_clips;
-	int N;
-};
-
-struct MagArgs {
-	const float* rows;
-	float* v; // rows of v_stride floats; the floats behind bin H are written as +0
-	size_t v_stride, frames; // frames = n_clips * m
-	int N;
-};
+using zen_addon::FrameArgs; // ../addon/stft_args.h, with the layout of a call's rows
+using zen_addon::MagArgs;
 
 struct SimArgs { // S[a][b] for the ma rows of va against the mb rows of vb (both rows of `bins` floats, v_stride apart)
 	const float* va;
@@ -69,8 +59,10 @@ struct OlaArgs { // one clip
 	int N;
 };
 
-hipError_t launch_frame(const FrameArgs& a, hipStream_t s);
-hipError_t launch_magnitude(const MagArgs& a, hipStream_t s);
+// the first two are ../addon/stft_kernels.h's as this library compiled them; hidden: their names spell a type of zen_addon,
+// and nothing of zen_amd/addon is among a library's dynamic symbols
+__attribute__((visibility("hidden"))) hipError_t launch_frame(const FrameArgs& a, hipStream_t s);
+__attribute__((visibility("hidden"))) hipError_t launch_magnitude(const MagArgs& a, hipStream_t s);
 hipError_t launch_similarity(const SimArgs& a, bool mfma, hipStream_t s);
 hipError_t launch_select(const SelectArgs& a, hipStream_t s);
 hipError_t launch_gather_median(const GatherArgs& a, hipStream_t s);

@@ -8,14 +8,17 @@
 // order the contract fixes (D, over the bins) is an fma chain in that order on both routes: v_mfma_f32_32x32x2_f32 adds its
 // two products in k order with one rounding each, and the K loop feeds it the bins in rising order.  A median is a selection:
 // it is exact however it is found, so the two paths of gather_median (a sorting network in registers, a search by rank through
-// lane-private columns in LDS) give the same values.  frame, magnitude, mask and overlap_add are zen_amd/repet's, copied:
-// that library's files are pinned, and zen_amd/addon holds no kernels.
+// lane-private columns in LDS) give the same values.  frame, magnitude, the body of mask, the sample of overlap_add and the
+// loader of the similarity's LDS tiles are zen_amd/addon/stft_kernels.h's, the network and the register path of the median
+// zen_amd/addon/median_select.h's: shared with zen_amd/repet and nmf.
 #include <hip/hip_runtime.h>
 
 #include <limits.h>
 #include <math.h>
 #include <stdint.h>
 
+#include "../addon/median_select.h"
+#include "../addon/stft_kernels.h"
 #include "repsim_kernels.h"
 
 #pragma clang fp contract(off)
@@ -23,43 +26,7 @@
 namespace zen_repsim {
 namespace {
 
-constexpr int TPB = 256;
-
-unsigned clip_rows(size_t n_clips) { return (unsigned)(n_clips < 65535 ? n_clips : 65535); }
-
-// ------------------------------------------------------------------------------------------------ frame
-// xp is H zeros, the clip, zeros: sample j of frame k is x[k H - H + j]
-__global__ __launch_bounds__(TPB) void frame_kernel(FrameArgs k)
-{
-	const int N = k.N, H = N / 2;
-	const size_t f = blockIdx.x;
-	for (size_t c = blockIdx.y; c < k.n_clips; c += gridDim.y) {
-		const float* __restrict__ x = k.in + c * k.in_stride;
-		float2* __restrict__ row = reinterpret_cast<float2*>(k.rows) + (c * k.m + f) * (size_t)N;
-		for (int j = threadIdx.x; j < N; j += TPB) {
-			const size_t pos = f * (size_t)H + (size_t)j; // index into xp
-			const float v = pos >= (size_t)H && pos - H < k.n ? x[pos - H] : 0.0f;
-			row[j] = make_float2(v * k.win[j], 0.0f);
-		}
-	}
-}
-
-// ------------------------------------------------------------------------------------------------ magnitude
-__global__ __launch_bounds__(TPB) void magnitude_kernel(MagArgs k)
-{
-	const int N = k.N, H = N / 2;
-	const size_t f = blockIdx.x;
-	const float2* __restrict__ row = reinterpret_cast<const float2*>(k.rows) + f * (size_t)N;
-	float* __restrict__ v = k.v + f * k.v_stride;
-	for (size_t i = threadIdx.x; i < k.v_stride; i += TPB) {
-		float r = 0.0f;
-		if (i <= (size_t)H) {
-			const float2 z = row[i];
-			r = sqrtf(z.x * z.x + z.y * z.y);
-		}
-		v[i] = r;
-	}
-}
+using namespace zen_addon;
 
 // ------------------------------------------------------------------------------------------------ similarity
 // A workgroup of four waves computes a SIM_TILE x SIM_TILE block of S: wave w the 64 x 64 quadrant (w >> 1, w & 1) as 2 x 2
@@ -71,45 +38,7 @@ __global__ __launch_bounds__(TPB) void magnitude_kernel(MagArgs k)
 // Both routes keep a result in the same lane and register (the matrix core's C/D map: column = lane & 31,
 // row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)), so they share the epilogue.  The norms of the block's 2 x 128 rows are the
 // same chain with both factors one row, carried by one thread per row beside the products: 1/128 of the block's work.
-constexpr int KC = 32;
-constexpr int LDK = KC + 1;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-template <bool VEC>
-__device__ __forceinline__ void load_tile(float* __restrict__ T, const float* __restrict__ v, size_t v_stride, size_t r0, size_t rows, size_t f0,
-                                          size_t bins, float pad, int tid)
-{
-	if (VEC) { // v 16-byte aligned, v_stride a multiple of 4
-#pragma unroll
-		for (int i = 0; i < SIM_TILE * KC / 4 / TPB; ++i) {
-			const int s = tid + TPB * i, r = s >> 3, q = (s & 7) * 4;
-			const size_t row = r0 + r, f = f0 + q;
-			float4 x = make_float4(pad, pad, pad, pad);
-			if (row < rows) {
-				const float* __restrict__ p = v + row * v_stride + f;
-				if (f + 4 <= bins) {
-					x = *reinterpret_cast<const float4*>(p);
-				} else {
-					x.x = f < bins ? p[0] : pad;
-					x.y = f + 1 < bins ? p[1] : pad;
-					x.z = f + 2 < bins ? p[2] : pad;
-				}
-			}
-			float* __restrict__ d = T + r * LDK + q;
-			d[0] = x.x;
-			d[1] = x.y;
-			d[2] = x.z;
-			d[3] = x.w;
-		}
-	} else {
-#pragma unroll
-		for (int i = 0; i < SIM_TILE * KC / TPB; ++i) {
-			const int e = tid + TPB * i, r = e >> 5, q = e & 31;
-			const size_t row = r0 + r, f = f0 + q;
-			T[r * LDK + q] = row < rows && f < bins ? v[row * v_stride + f] : pad;
-		}
-	}
-}
 
 template <bool MFMA, bool VEC>
 __global__ __launch_bounds__(TPB) void similarity_kernel(SimArgs k)
@@ -132,8 +61,8 @@ __global__ __launch_bounds__(TPB) void similarity_kernel(SimArgs k)
 	float nn = 0.0f; // D[row][row] of row tid of the a side, tid - SIM_TILE of the b side
 	const float* __restrict__ mine = tid < SIM_TILE ? As + tid * LDK : Bs + (tid - SIM_TILE) * LDK;
 	for (size_t f0 = 0; f0 < k.bins; f0 += KC) {
-		load_tile<VEC>(As, k.va, k.v_stride, a0, k.ma, f0, k.bins, -0.0f, tid);
-		load_tile<VEC>(Bs, k.vb, k.v_stride, b0, k.mb, f0, k.bins, 0.0f, tid);
+		load_tile<SIM_TILE, VEC>(As, k.va, k.v_stride, a0, k.ma, f0, k.bins, -0.0f, tid);
+		load_tile<SIM_TILE, VEC>(Bs, k.vb, k.v_stride, b0, k.mb, f0, k.bins, 0.0f, tid);
 		__syncthreads();
 #pragma unroll
 		for (int kk = 0; kk < KC; ++kk)
@@ -293,95 +222,20 @@ __global__ __launch_bounds__(TPB) void select_kernel(SelectArgs k)
 }
 
 // ------------------------------------------------------------------------------------------------ gather median
-__device__ __forceinline__ void cswap(float& a, float& b) // a permutation of (a, b) for every pair of non-NaN values
-{
-	const bool gt = a > b;
-	const float lo = gt ? b : a, hi = gt ? a : b;
-	a = lo;
-	b = hi;
-}
-
-template <int P>
-__device__ __forceinline__ void sort_network(float (&a)[P]) // the bitonic network on P values, ascending
-{
-#pragma unroll
-	for (int k = 2; k <= P; k <<= 1) {
-#pragma unroll
-		for (int j = k >> 1; j > 0; j >>= 1) {
-#pragma unroll
-			for (int i = 0; i < P; ++i) {
-				const int l = i ^ j;
-				if (l > i) {
-					if ((i & k) == 0)
-						cswap(a[i], a[l]);
-					else
-						cswap(a[l], a[i]);
-				}
-			}
-		}
-	}
-}
-
-template <int P>
-__device__ __forceinline__ float pick_median(const float (&a)[P], int c) // c values sorted in front of P - c times +inf
-{
-	const int lo = (c - 1) >> 1, hi = c >> 1;
-	float slo = a[0], shi = a[0];
-#pragma unroll
-	for (int i = 1; i < P; ++i) { // every index is a constant: the values stay in registers
-		slo = i == lo ? a[i] : slo;
-		shi = i == hi ? a[i] : shi;
-	}
-	return (c & 1) ? slo : (slo + shi) * 0.5f;
-}
-
 __device__ __forceinline__ int clamp_count(int c, int k) { return c < 0 ? 0 : c > k ? k : c; }
 __device__ __forceinline__ size_t clamp_frame(int j, size_t m) { return j < 0 ? 0 : (size_t)j >= m ? m - 1 : (size_t)j; }
 
-// c values of frame a in registers, P >= c.  A lane has VEC adjacent bins: every gathered frame q is a coalesced row read (16
-// bytes per lane for VEC = 4) and the VEC networks are independent of each other.
-template <int P, int VEC>
-__device__ __forceinline__ void median_in_registers(const GatherArgs& k, const int* __restrict__ idx, float* __restrict__ out, size_t f, int c)
-{
-	float a[VEC][P];
-	const bool whole = VEC == 1 || f + VEC <= k.bins;
-#pragma unroll
-	for (int q = 0; q < P; ++q) {
-		const bool in = q < c;
-		const float* __restrict__ src = k.v + (in ? clamp_frame(idx[q], k.m) : 0) * k.v_stride + f;
-		if (VEC == 4 && whole) {
-			float4 x = make_float4(INFINITY, INFINITY, INFINITY, INFINITY);
-			if (in)
-				x = *reinterpret_cast<const float4*>(src);
-			a[0][q] = x.x;
-			a[1 % VEC][q] = x.y;
-			a[2 % VEC][q] = x.z;
-			a[3 % VEC][q] = x.w;
-		} else {
-#pragma unroll
-			for (int e = 0; e < VEC; ++e)
-				a[e][q] = in && f + e < k.bins ? src[e] : INFINITY;
-		}
-	}
-	float r[VEC];
-#pragma unroll
-	for (int e = 0; e < VEC; ++e) {
-		sort_network<P>(a[e]);
-		r[e] = pick_median<P>(a[e], c);
-	}
-	if (VEC == 4 && whole) {
-		*reinterpret_cast<float4*>(out) = make_float4(r[0], r[1 % VEC], r[2 % VEC], r[3 % VEC]);
-	} else {
-#pragma unroll
-		for (int e = 0; e < VEC; ++e)
-			if (f + e < k.bins)
-				out[e] = r[e];
-	}
-}
+struct GatheredRows { // row q of the median of a frame: the q-th frame its selection names, q < c
+	const GatherArgs& k;
+	const int* __restrict__ idx;
+	int c;
+	__device__ bool present(int q) const { return q < c; }
+	__device__ const float* row(int q) const { return k.v + (q < c ? clamp_frame(idx[q], k.m) : 0) * k.v_stride; } // idx has c entries
+};
 
-// The frames of up to REGISTER_NEIGHBOURS neighbours: a wave per frame, the network picked by the frame's count (the same
-// for the whole wave).  Frames with more leave at once: median_lds_kernel has them.  VEC = 4 wants v and u 16-byte aligned
-// and both strides multiples of 4; the lanes at the end of a row fall back to single words.
+// The frames of up to REGISTER_NEIGHBOURS neighbours: a wave per frame, a lane has VEC adjacent bins (median_select.h), the
+// network picked by the frame's count (the same for the whole wave).  Frames with more leave at once: median_lds_kernel has
+// them.  VEC = 4 wants v and u 16-byte aligned and both strides multiples of 4.
 template <int VEC>
 __global__ __launch_bounds__(TPB) void median_reg_kernel(GatherArgs k)
 {
@@ -392,7 +246,7 @@ __global__ __launch_bounds__(TPB) void median_reg_kernel(GatherArgs k)
 	const int c = clamp_count(k.counts[a], k.k);
 	if (c > REGISTER_NEIGHBOURS)
 		return;
-	const int* __restrict__ idx = k.idx + a * (size_t)k.k;
+	const GatheredRows rows = {k, k.idx + a * (size_t)k.k, c};
 	float* __restrict__ out = k.u + a * k.u_stride + f;
 	if (c == 0) {
 #pragma unroll
@@ -400,15 +254,15 @@ __global__ __launch_bounds__(TPB) void median_reg_kernel(GatherArgs k)
 			if (f + e < k.bins)
 				out[e] = 0.0f;
 	} else if (c <= 2) {
-		median_in_registers<2, VEC>(k, idx, out, f, c);
+		median_in_registers<2, VEC>(rows, f, k.bins, out);
 	} else if (c <= 4) {
-		median_in_registers<4, VEC>(k, idx, out, f, c);
+		median_in_registers<4, VEC>(rows, f, k.bins, out);
 	} else if (c <= 8) {
-		median_in_registers<8, VEC>(k, idx, out, f, c);
+		median_in_registers<8, VEC>(rows, f, k.bins, out);
 	} else if (c <= 16) {
-		median_in_registers<16, VEC>(k, idx, out, f, c);
+		median_in_registers<16, VEC>(rows, f, k.bins, out);
 	} else {
-		median_in_registers<REGISTER_NEIGHBOURS, VEC>(k, idx, out, f, c);
+		median_in_registers<REGISTER_NEIGHBOURS, VEC>(rows, f, k.bins, out);
 	}
 }
 
@@ -470,63 +324,28 @@ __global__ __launch_bounds__(64) void median_lds_kernel(GatherArgs k)
 // ------------------------------------------------------------------------------------------------ mask
 __global__ __launch_bounds__(TPB) void mask_kernel(MaskArgs k)
 {
-	const int N = k.N, H = N / 2;
-	const size_t fr = blockIdx.x;
-	float2* __restrict__ row = reinterpret_cast<float2*>(k.rows) + fr * (size_t)N;
-	const float* __restrict__ v = k.v + fr * k.v_stride;
-	const float* __restrict__ u = k.u + fr * k.v_stride;
-	for (int f = threadIdx.x; f <= H; f += TPB) {
-		const float V = v[f], U = u[f];
-		const float W = U < V ? U : V;
-		float M = V > 0.0f ? W / V : 0.0f;
-		if (f < k.kc)
-			M = 1.0f;
-		const float2 z = row[f];
-		row[f] = make_float2(z.x * M, z.y * M);
-		if (f > 0 && f < H) {
-			const float2 y = row[N - f];
-			row[N - f] = make_float2(y.x * M, y.y * M);
-		}
-	}
+	const size_t fr = blockIdx.x; // the model of a frame is its own row of U
+	soft_mask_frame(reinterpret_cast<float2*>(k.rows) + fr * (size_t)k.N, k.v + fr * k.v_stride, k.u + fr * k.v_stride, k.N, k.kc);
 }
 
 // ------------------------------------------------------------------------------------------------ overlap-add
 __global__ __launch_bounds__(TPB) void overlap_add_kernel(OlaArgs k)
 {
-	const int N = k.N, H = N / 2;
 	const size_t t = (size_t)blockIdx.x * TPB + threadIdx.x;
 	if (t >= k.n)
 		return;
 	const float x = k.in[t];
-	const size_t fr = t / H;
-	const int i = (int)(t % H);
-	const float2* __restrict__ g = reinterpret_cast<const float2*>(k.rows);
-	const float bg = (g[fr * N + H + i].x + g[(fr + 1) * N + i].x) / k.div[i]; // the earlier frame first
+	const float bg = overlap_add_sample(k.rows, k.div, t, k.N);
 	if (k.background)
 		k.background[t] = bg;
 	if (k.foreground)
 		k.foreground[t] = x - bg;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 } // namespace
 
-hipError_t launch_frame(const FrameArgs& a, hipStream_t s)
-{
-	if (a.m == 0 || a.n_clips == 0)
-		return hipSuccess;
-	frame_kernel<<<dim3((unsigned)a.m, clip_rows(a.n_clips), 1), TPB, 0, s>>>(a);
-	return hipGetLastError();
-}
-
-hipError_t launch_magnitude(const MagArgs& a, hipStream_t s)
-{
-	if (a.frames == 0)
-		return hipSuccess;
-	magnitude_kernel<<<dim3((unsigned)a.frames, 1, 1), TPB, 0, s>>>(a);
-	return hipGetLastError();
-}
+hipError_t launch_frame(const FrameArgs& a, hipStream_t s) { return zen_addon::launch_frame(a, s); }
+hipError_t launch_magnitude(const MagArgs& a, hipStream_t s) { return zen_addon::launch_magnitude(a, s); }
 
 hipError_t launch_similarity(const SimArgs& a, bool mfma, hipStream_t s)
 {
