@@ -17,11 +17,12 @@ NAMES = ("pcm", "ragged", "live", "pitch")
 def addons():
     """the four libraries, built where absent"""
     from zen_amd import addon_build
-    assert tuple(addon_build.ADDONS) == NAMES
-    for a in addon_build.ADDONS.values():
+    assert tuple(addon_build.LIBRARIES)[:4] == NAMES
+    four = {n: addon_build.LIBRARIES[n] for n in NAMES}
+    for a in four.values():
         if not os.path.exists(a.OUT):
             a.build()
-    return addon_build.ADDONS
+    return four
 
 
 # ---- one error message per library ------------------------------------------------------------------------------------------
@@ -102,8 +103,27 @@ def test_former_builder_names_are_the_table_entries():
     from zen_amd import addon_build
     for n in NAMES:
         a = getattr(zen_amd, n + "_build")
-        assert a is addon_build.ADDONS[n] and a.OUT.endswith("libzen_hip_%s.so" % n) and os.path.isdir(a.SRC) and callable(a.build)
-    assert zen_amd.pitch_build.build_demo is addon_build.build_demo
+        assert a is addon_build.LIBRARIES[n] and a.OUT.endswith("libzen_hip_%s.so" % n) and os.path.isdir(a.SRC) and callable(a.build)
+    assert zen_amd.pitch_build.DEMO.endswith(os.path.join("bin", "pitch-track")) and callable(zen_amd.pitch_build.build_demo)
+    assert all(getattr(zen_amd, n + "_build").DEMO is None for n in ("pcm", "ragged", "live"))
+
+
+EVERY_NAME = ("pcm", "ragged", "live", "pitch", "blockrun", "beat", "multi", "repet", "cqt", "repsim", "nmf", "tsm", "resample")
+
+
+def test_one_table_holds_every_library():
+    """the thirteen in the order they are built, in the module's only dictionary of Addons, one entry per library directory on
+    disk; every entry is the module-level object of its name and shares the one list of flags"""
+    from zen_amd import addon_build
+    tables = [k for k, v in vars(addon_build).items() if isinstance(v, dict) and v and all(isinstance(a, addon_build.Addon) for a in v.values())]
+    assert tables == ["LIBRARIES"]
+    assert tuple(addon_build.LIBRARIES) == EVERY_NAME
+    for n, a in addon_build.LIBRARIES.items():
+        assert a is getattr(addon_build, n) and a.name == n and a.FLAGS is addon_build.FLAGS
+    pkg = os.path.join(ROOT, "zen_amd")
+    on_disk = {d for d in os.listdir(pkg) if os.path.exists(os.path.join(pkg, d, "zen_hip_%s.h" % d))}
+    assert on_disk == set(EVERY_NAME)
+    assert {n for n, a in addon_build.LIBRARIES.items() if a.DEMO is None} == {"pcm", "ragged", "live", "blockrun"}
 
 
 def mtimes(addons):
@@ -136,3 +156,42 @@ def test_builder_recompiles_what_is_stale_and_nothing_else(addons):
     for a in addons.values():
         a.build()
     assert mtimes(addons) == after
+
+
+# ---- the calls every handle answers, refused the same way in every library ----------------------------------------------------
+HANDLE_LIBRARIES = ("pitch", "beat", "live", "ragged", "repet", "cqt", "repsim", "nmf", "tsm", "resample")
+
+
+@pytest.mark.parametrize("name", HANDLE_LIBRARIES)
+def test_null_handles_are_refused_with_the_librarys_own_words(name):
+    """set_stream, profile, profile_get and stats on a null handle, without a device: the code and the message each library
+    has always given (ragged has no stats call)"""
+    import importlib
+    L = importlib.import_module("zen_amd." + name).load()
+    err = getattr(L, "zen_hip_%s_last_error" % name)
+    call = lambda fn, *args: (getattr(L, "zen_hip_%s_%s" % (name, fn))(*args), err().decode())   # noqa: E731
+    assert call("set_stream", None, None) == (2, "%s_set_stream: null handle" % name)
+    assert call("profile", None, 1) == (2, "null handle")
+    assert call("profile_get", None, None, None, None) == (2, "%s_profile_get: null argument" % name)
+    if name != "ragged":
+        assert call("stats", None, None) == (2, "%s_stats: null argument" % name)
+
+
+# ---- the programs ---------------------------------------------------------------------------------------------------------------
+PROGRAMS = {"pitch": ("pitch-track", []), "beat": ("beat-track", []), "multi": ("zen-stems", []), "repet": ("zen-repet", ["-o", "out"]),
+            "cqt": ("zen-cqt", ["-o", "out"]), "repsim": ("zen-repsim", ["-o", "out"]), "nmf": ("zen-nmf", ["-o", "out.znmf"]),
+            "tsm": ("zen-stretch", ["-a", "1.5", "-o", "out.wav"]), "resample": ("zen-shift", ["-s", "3", "-o", "out.wav"])}
+
+
+@pytest.mark.parametrize("name", sorted(PROGRAMS))
+def test_program_reports_a_file_it_cannot_open(name, tmp_path):
+    """every program reads its recording before it touches a device: a path that does not exist ends it with status 1 and one
+    line, the program's name in front of cli/wav.h's message"""
+    from zen_amd import addon_build
+    prog, args = PROGRAMS[name]
+    exe = addon_build.LIBRARIES[name].build_demo()
+    assert exe.endswith(os.path.join("bin", prog))
+    missing = str(tmp_path / "absent.wav")
+    argv = [exe] + (["train"] if name == "nmf" else []) + [missing] + args
+    r = subprocess.run(argv, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, cwd=str(tmp_path))
+    assert (r.returncode, r.stdout, r.stderr) == (1, "", "%s: cannot open %s\n" % (prog, missing))

@@ -73,8 +73,8 @@ def test_library_loads_without_gpu_and_checks_arguments_first(beat_so):
 def test_beat_is_registered_beside_the_four():
     import zen_amd
     from zen_amd import addon_build
-    assert "beat" not in addon_build.ADDONS and addon_build.ALL_ADDONS["beat"] is addon_build.beat is zen_amd.beat_build
-    assert addon_build.beat.FLAGS is addon_build.FLAGS and addon_build.beat.build_demo is addon_build.build_beat_demo
+    assert addon_build.LIBRARIES["beat"] is addon_build.beat is zen_amd.beat_build
+    assert addon_build.beat.FLAGS is addon_build.FLAGS and addon_build.beat.DEMO.endswith(os.path.join("bin", "beat-track"))
     assert zen_amd.beat.Beat and addon_build.beat.OUT.endswith("libzen_hip_beat.so")
 
 
@@ -141,7 +141,7 @@ def test_build_keeps_the_arithmetic_contract_and_the_engines_apart():
         text = open(os.path.join(addon.SRC, name)).read()
         assert "csrc/" not in re.sub(r"//.*", "", text), name
         for inc in re.findall(r'#include "([^"]+)"', text):
-            assert inc in ("zen_hip.h", "zen_hip_beat.h", "beat_kernels.h", "beat_tables.h", "wav.h", "../addon/addon_host.h"), (name, inc)
+            assert inc in ("zen_hip.h", "zen_hip_beat.h", "beat_kernels.h", "beat_tables.h", "wav.h", "demo.h", "../addon/addon_host.h"), (name, inc)
     assert sorted(os.listdir(os.path.join(ROOT, "zen_amd", "addon"))) == ["addon_host.h", "hpri_pair.h", "median_select.h", "row_walk.h", "stft_args.h", "stft_host.h", "stft_kernels.h"]
 
 

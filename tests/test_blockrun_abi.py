@@ -71,7 +71,7 @@ def test_header_compiles_as_c99(tmp_path):
 def test_build_keeps_the_arithmetic_contract_and_is_registered():
     from zen_amd import addon_build
     a = addon_build.blockrun
-    assert addon_build.ALL_ADDONS["blockrun"] is a and a.OUT.endswith("libzen_hip_blockrun.so")
+    assert addon_build.LIBRARIES["blockrun"] is a and a.DEMO is None and a.OUT.endswith("libzen_hip_blockrun.so")
     flags = a.FLAGS + a.FILE_FLAGS["blockrun_kernel.hip"]
     assert "-ffp-contract=off" in flags and "-fno-fast-math" in flags
     assert not any("fast-math" in f and f != "-fno-fast-math" for f in flags)

@@ -228,6 +228,20 @@ def test_addon_median_selection_on_the_host(tmp_path):
     assert r.returncode == 0 and "passed" in r.stdout and not r.stderr, (r.stdout[-2000:], r.stderr[-2000:])
 
 
+def test_demo_frame_on_the_host(tmp_path):
+    """zen_amd/cli/demo.h, the frame of the add-ons' demo programs, behind stubs of the zen_hip_* functions it names
+    (tests/cpp/test_demo_host.cpp), with the address and undefined-behaviour sanitizers: the option parsers on "12", "12x",
+    "", "-1" and "1e3" (and against strtoull / strtol / strtod / strtof themselves), load_mono on a mono and a stereo PCM16
+    file against wav.h called directly, peak_normalise on zeros and on a negative peak, and the runner's exits 0, 1 and 86
+    with their lines on stderr."""
+    exe = str(tmp_path / "test_demo_host")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "zen_amd", "cli"),
+                           os.path.join(ROOT, "tests", "cpp", "test_demo_host.cpp"), "-o", exe])
+    r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "passed" in r.stdout and not r.stderr, (r.stdout[-2000:], r.stderr[-2000:])
+
+
 def test_block_merge_selection_on_the_host(tmp_path):
     """zen_amd/csrc/median_big.h compiled as plain C++ (tests/cpp/test_median_big_host.cpp): zbig::medians_big<W> for every long
     mask the kernels instantiate (65 .. 257 taps), through a loader of sorted 16-blocks and through one that also hands out

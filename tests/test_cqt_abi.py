@@ -139,11 +139,9 @@ def test_library_loads_without_gpu_and_checks_arguments_first(cqt_so):
 def test_cqt_is_registered_beside_the_others():
     import zen_amd
     from zen_amd import addon_build
-    assert tuple(addon_build.ADDONS) == ("pcm", "ragged", "live", "pitch")
-    assert "cqt" in addon_build.LATER_ADDONS and addon_build.ALL_ADDONS["cqt"] is addon_build.cqt is zen_amd.cqt_build
-    assert addon_build.cqt.FLAGS is addon_build.FLAGS and addon_build.cqt.build_demo is addon_build.build_cqt_demo
+    assert addon_build.LIBRARIES["cqt"] is addon_build.cqt is zen_amd.cqt_build
+    assert addon_build.cqt.FLAGS is addon_build.FLAGS and addon_build.cqt.DEMO.endswith(os.path.join("bin", "zen-cqt"))
     assert zen_amd.cqt.Cqt and addon_build.cqt.OUT.endswith("libzen_hip_cqt.so")
-    assert list(addon_build.LATER_ADDONS)[:3] == ["beat", "multi", "repet"]
 
 
 def test_library_finds_the_engine_library_beside_itself(cqt_so):
@@ -170,7 +168,7 @@ def test_build_keeps_the_arithmetic_contract_and_the_engines_apart():
         text = open(os.path.join(addon.SRC, name)).read()
         assert "csrc/" not in re.sub(r"//.*", "", text), name
         for inc in re.findall(r'#include "([^"]+)"', text):
-            assert inc in ("zen_hip.h", "zen_hip_cqt.h", "cqt_kernels.h", "wav.h", "../addon/addon_host.h"), (name, inc)
+            assert inc in ("zen_hip.h", "zen_hip_cqt.h", "cqt_kernels.h", "wav.h", "demo.h", "../addon/addon_host.h"), (name, inc)
     assert sorted(os.listdir(os.path.join(ROOT, "zen_amd", "addon"))) == ["addon_host.h", "hpri_pair.h", "median_select.h", "row_walk.h", "stft_args.h", "stft_host.h", "stft_kernels.h"]
 
 

@@ -103,11 +103,9 @@ def test_binding_refuses_shapes_and_dtypes_before_the_library():
 def test_multi_is_registered_beside_beat():
     import zen_amd
     from zen_amd import addon_build
-    assert tuple(addon_build.ADDONS) == ("pcm", "ragged", "live", "pitch")
-    assert "multi" not in addon_build.ADDONS and "multi" in addon_build.LATER_ADDONS and "beat" in addon_build.LATER_ADDONS
-    assert addon_build.ALL_ADDONS["multi"] is addon_build.multi is zen_amd.multi_build
+    assert addon_build.LIBRARIES["multi"] is addon_build.multi is zen_amd.multi_build
     assert addon_build.multi.FLAGS is addon_build.FLAGS and not addon_build.multi.FILE_FLAGS
-    assert addon_build.multi.build_demo is addon_build.build_stems_demo
+    assert addon_build.multi.DEMO.endswith(os.path.join("bin", "zen-stems"))
     assert addon_build.multi.SOURCES == ["multi_kernels.hip", "multi.hip"]
     assert os.path.join(ROOT, "zen_amd", "pcm", "pcm_convert.h") in addon_build.multi.deps()
     assert zen_amd.multi.Offline and zen_amd.multi.Realtime and addon_build.multi.OUT.endswith("libzen_hip_multi.so")
@@ -130,7 +128,7 @@ def test_sources_see_the_listed_headers_only_and_nothing_of_the_engines():
     from zen_amd.addon_build import multi as addon
     assert "-ffp-contract=off" in addon.FLAGS and "-fno-fast-math" in addon.FLAGS
     assert sorted(os.listdir(addon.SRC)) == ["multi.hip", "multi_kernels.h", "multi_kernels.hip", "multi_stems.cpp", "zen_hip_multi.h"]
-    allowed = ("zen_hip.h", "zen_hip_multi.h", "multi_kernels.h", "wav.h", "../addon/addon_host.h", "../pcm/pcm_convert.h")
+    allowed = ("zen_hip.h", "zen_hip_multi.h", "multi_kernels.h", "wav.h", "demo.h", "../addon/addon_host.h", "../pcm/pcm_convert.h")
     for name in os.listdir(addon.SRC):
         text = open(os.path.join(addon.SRC, name)).read()
         assert "csrc/" not in re.sub(r"//.*", "", text), name

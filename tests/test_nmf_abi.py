@@ -136,13 +136,10 @@ def test_the_kernels_alone_refuse_before_a_device_is_touched(nmf_so):
 def test_nmf_is_registered_behind_the_others_and_the_pinned_tables_stand():
     import zen_amd
     from zen_amd import addon_build
-    assert tuple(addon_build.ADDONS) == ("pcm", "ragged", "live", "pitch")
-    assert tuple(addon_build.LATER_ADDONS) == ("beat", "multi", "repet", "cqt", "repsim")
-    assert list(addon_build.ALL_ADDONS)[-1] == "nmf" and len(addon_build.ALL_ADDONS) == 11
-    assert addon_build.ALL_ADDONS["nmf"] is addon_build.nmf is zen_amd.nmf_build
+    assert addon_build.LIBRARIES["nmf"] is addon_build.nmf is zen_amd.nmf_build
     assert addon_build.nmf.SOURCES == ["nmf_kernels.hip", "nmf.hip"]
     assert addon_build.nmf.FLAGS is addon_build.FLAGS and not addon_build.nmf.FILE_FLAGS
-    assert addon_build.nmf.build_demo is addon_build.build_nmf_demo
+    assert addon_build.nmf.DEMO.endswith(os.path.join("bin", "zen-nmf"))
     from zen_amd import nmf
     assert nmf.Nmf and addon_build.nmf.OUT.endswith("libzen_hip_nmf.so")
 
@@ -202,7 +199,7 @@ def test_build_keeps_the_arithmetic_contract_and_the_other_libraries_apart():
         assert "csrc/" not in re.sub(r"//.*", "", text), name
         assert "asm" not in re.sub(r"//.*", "", text).split(), name
         for inc in re.findall(r'#include "([^"]+)"', text):
-            assert inc in ("zen_hip.h", "zen_hip_nmf.h", "nmf_kernels.h", "wav.h", "../addon/addon_host.h", "../addon/stft_host.h", "../addon/stft_args.h",
+            assert inc in ("zen_hip.h", "zen_hip_nmf.h", "nmf_kernels.h", "wav.h", "demo.h", "../addon/addon_host.h", "../addon/stft_host.h", "../addon/stft_args.h",
                            "../addon/stft_kernels.h"), (name, inc)
     zen = os.path.join(ROOT, "zen_amd")
     assert sorted(os.listdir(os.path.join(zen, "addon"))) == ["addon_host.h", "hpri_pair.h", "median_select.h", "row_walk.h", "stft_args.h", "stft_host.h", "stft_kernels.h"]

@@ -74,7 +74,7 @@ def test_build_keeps_the_arithmetic_contract_and_the_engines_apart():
         text = open(os.path.join(addon.SRC, name)).read()
         assert "csrc/" not in re.sub(r"//.*", "", text), name
         for inc in re.findall(r'#include "([^"]+)"', text):
-            assert inc in ("zen_hip.h", "zen_hip_pitch.h", "pitch_kernels.h", "wav.h", "../addon/addon_host.h"), (name, inc)
+            assert inc in ("zen_hip.h", "zen_hip_pitch.h", "pitch_kernels.h", "wav.h", "demo.h", "../addon/addon_host.h"), (name, inc)
 
 
 def test_demo_program_is_built_and_states_its_usage(pitch_so):

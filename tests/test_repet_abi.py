@@ -88,9 +88,8 @@ def test_library_loads_without_gpu_and_checks_arguments_first(repet_so):
 def test_repet_is_registered_beside_the_others():
     import zen_amd
     from zen_amd import addon_build
-    assert tuple(addon_build.ADDONS) == ("pcm", "ragged", "live", "pitch")
-    assert "repet" in addon_build.LATER_ADDONS and addon_build.ALL_ADDONS["repet"] is addon_build.repet is zen_amd.repet_build
-    assert addon_build.repet.FLAGS is addon_build.FLAGS and addon_build.repet.build_demo is addon_build.build_repet_demo
+    assert addon_build.LIBRARIES["repet"] is addon_build.repet is zen_amd.repet_build
+    assert addon_build.repet.FLAGS is addon_build.FLAGS and addon_build.repet.DEMO.endswith(os.path.join("bin", "zen-repet"))
     assert zen_amd.repet.Repet and addon_build.repet.OUT.endswith("libzen_hip_repet.so")
 
 
@@ -192,7 +191,7 @@ def test_build_keeps_the_arithmetic_contract_and_the_engines_apart():
         text = open(os.path.join(addon.SRC, name)).read()
         assert "csrc/" not in re.sub(r"//.*", "", text) and "median_net.h" not in text, name
         for inc in re.findall(r'#include "([^"]+)"', text):
-            assert inc in ("zen_hip.h", "zen_hip_repet.h", "repet_kernels.h", "wav.h", "../addon/addon_host.h", "../addon/stft_host.h", "../addon/stft_args.h",
+            assert inc in ("zen_hip.h", "zen_hip_repet.h", "repet_kernels.h", "wav.h", "demo.h", "../addon/addon_host.h", "../addon/stft_host.h", "../addon/stft_args.h",
                            "../addon/stft_kernels.h", "../addon/median_select.h"), (name, inc)
     assert sorted(os.listdir(os.path.join(ROOT, "zen_amd", "addon"))) == ["addon_host.h", "hpri_pair.h", "median_select.h", "row_walk.h", "stft_args.h", "stft_host.h", "stft_kernels.h"]
 

@@ -111,11 +111,9 @@ def test_the_kernels_alone_refuse_before_a_device_is_touched(repsim_so):
 def test_repsim_is_registered_behind_the_others():
     import zen_amd
     from zen_amd import addon_build
-    assert tuple(addon_build.ADDONS) == ("pcm", "ragged", "live", "pitch")
-    assert tuple(addon_build.LATER_ADDONS) == ("beat", "multi", "repet", "cqt", "repsim")
-    assert addon_build.ALL_ADDONS["repsim"] is addon_build.repsim is zen_amd.repsim_build
+    assert addon_build.LIBRARIES["repsim"] is addon_build.repsim is zen_amd.repsim_build
     assert addon_build.repsim.FLAGS is addon_build.FLAGS and not addon_build.repsim.FILE_FLAGS
-    assert addon_build.repsim.build_demo is addon_build.build_repsim_demo
+    assert addon_build.repsim.DEMO.endswith(os.path.join("bin", "zen-repsim"))
     assert zen_amd.repsim.Repsim and addon_build.repsim.OUT.endswith("libzen_hip_repsim.so")
 
 
@@ -165,7 +163,7 @@ def test_build_keeps_the_arithmetic_contract_and_the_other_libraries_apart():
         text = open(os.path.join(addon.SRC, name)).read()
         assert "csrc/" not in re.sub(r"//.*", "", text) and "median_net.h" not in text, name
         for inc in re.findall(r'#include "([^"]+)"', text):
-            assert inc in ("zen_hip.h", "zen_hip_repsim.h", "repsim_kernels.h", "wav.h", "../addon/addon_host.h", "../addon/stft_host.h", "../addon/stft_args.h",
+            assert inc in ("zen_hip.h", "zen_hip_repsim.h", "repsim_kernels.h", "wav.h", "demo.h", "../addon/addon_host.h", "../addon/stft_host.h", "../addon/stft_args.h",
                            "../addon/stft_kernels.h", "../addon/median_select.h"), (name, inc)
     assert sorted(os.listdir(os.path.join(ROOT, "zen_amd", "addon"))) == ["addon_host.h", "hpri_pair.h", "median_select.h", "row_walk.h", "stft_args.h", "stft_host.h", "stft_kernels.h"]
     assert sorted(os.listdir(os.path.join(ROOT, "zen_amd", "repet"))) == ["repet.hip", "repet_kernels.h", "repet_kernels.hip", "repet_main.cpp",

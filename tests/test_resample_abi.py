@@ -152,17 +152,12 @@ def test_ratio_for_shift_is_the_models(resample_so):
 def test_resample_is_registered_in_a_table_of_its_own():
     import zen_amd
     from zen_amd import _addon, addon_build, resample
-    assert resample.load and tuple(addon_build.SHIFT_ADDONS) == ("resample",)
-    assert tuple(addon_build.ADDONS) == ("pcm", "ragged", "live", "pitch") and tuple(addon_build.ENGINE_ADDONS) == ("blockrun",)
-    assert tuple(addon_build.LATER_ADDONS) == ("beat", "multi", "repet", "cqt", "repsim") and tuple(addon_build.FACTOR_ADDONS) == ("nmf",)
-    assert len(addon_build.ALL_ADDONS) == 11 and tuple(addon_build.STRETCH_ADDONS) == ("tsm",)
-    assert list(addon_build.EVERY_ADDON) == list(addon_build.ALL_ADDONS) + ["tsm"] and "resample" not in addon_build.EVERY_ADDON
-    assert list(addon_build.EVERY_LIBRARY) == list(addon_build.EVERY_ADDON) + ["resample"]
-    assert addon_build.EVERY_LIBRARY["resample"] is addon_build.resample is zen_amd.resample_build
-    assert addon_build.resample.FLAGS is addon_build.FLAGS and addon_build.resample.build_demo is addon_build.build_shift_demo
+    assert resample.load and list(addon_build.LIBRARIES)[-2:] == ["tsm", "resample"]
+    assert addon_build.LIBRARIES["resample"] is addon_build.resample is zen_amd.resample_build
+    assert addon_build.resample.FLAGS is addon_build.FLAGS and tuple(addon_build.resample.demo_links) == ("tsm",)
     assert addon_build.resample.SOURCES == ["resample_kernels.hip", "resample.hip"] and addon_build.resample.OUT.endswith("libzen_hip_resample.so")
-    assert zen_amd.resample.Resampler and addon_build.SHIFT_DEMO.endswith(os.path.join("bin", "zen-shift"))
-    assert "EVERY_LIBRARY[name]" in open(_addon.__file__).read()
+    assert zen_amd.resample.Resampler and addon_build.resample.DEMO.endswith(os.path.join("bin", "zen-shift"))
+    assert "LIBRARIES[name]" in open(_addon.__file__).read()
 
 
 def test_library_finds_the_engine_library_beside_itself(resample_so):
@@ -191,7 +186,7 @@ def test_build_keeps_the_arithmetic_contract_and_the_engines_apart():
         text = open(os.path.join(addon.SRC, name)).read()
         code = re.sub(r"//.*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
         assert "csrc/" not in code and "asm" not in code and "atomic" not in code, name
-        allowed = ("zen_hip.h", "zen_hip_resample.h", "resample_kernels.h", "wav.h", "../addon/addon_host.h")
+        allowed = ("zen_hip.h", "zen_hip_resample.h", "resample_kernels.h", "wav.h", "demo.h", "../addon/addon_host.h")
         for inc in re.findall(r'#include "([^"]+)"', text):
             assert inc in allowed or (name == "resample_main.cpp" and inc == "zen_hip_tsm.h"), (name, inc)
     assert sorted(os.listdir(os.path.join(ROOT, "zen_amd", "addon"))) == ["addon_host.h", "hpri_pair.h", "median_select.h", "row_walk.h", "stft_args.h", "stft_host.h", "stft_kernels.h"]

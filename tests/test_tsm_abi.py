@@ -103,15 +103,10 @@ def test_library_loads_without_gpu_and_checks_arguments_first(tsm_so):
 def test_tsm_is_registered_in_a_table_of_its_own():
     import zen_amd
     from zen_amd import addon_build
-    assert tuple(addon_build.STRETCH_ADDONS) == ("tsm",)
-    assert tuple(addon_build.ADDONS) == ("pcm", "ragged", "live", "pitch") and tuple(addon_build.ENGINE_ADDONS) == ("blockrun",)
-    assert tuple(addon_build.LATER_ADDONS) == ("beat", "multi", "repet", "cqt", "repsim") and tuple(addon_build.FACTOR_ADDONS) == ("nmf",)
-    assert len(addon_build.ALL_ADDONS) == 11 and list(addon_build.ALL_ADDONS)[-1] == "nmf" and "tsm" not in addon_build.ALL_ADDONS
-    assert list(addon_build.EVERY_ADDON) == list(addon_build.ALL_ADDONS) + ["tsm"]
-    assert addon_build.EVERY_ADDON["tsm"] is addon_build.tsm is zen_amd.tsm_build
-    assert addon_build.tsm.FLAGS is addon_build.FLAGS and addon_build.tsm.build_demo is addon_build.build_stretch_demo
+    assert addon_build.LIBRARIES["tsm"] is addon_build.tsm is zen_amd.tsm_build
+    assert addon_build.tsm.FLAGS is addon_build.FLAGS and not addon_build.tsm.FILE_FLAGS
     assert addon_build.tsm.SOURCES == ["tsm_kernels.hip", "tsm.hip"] and addon_build.tsm.OUT.endswith("libzen_hip_tsm.so")
-    assert zen_amd.tsm.Tsm and addon_build.STRETCH_DEMO.endswith(os.path.join("bin", "zen-stretch"))
+    assert zen_amd.tsm.Tsm and addon_build.tsm.DEMO.endswith(os.path.join("bin", "zen-stretch"))
 
 
 @pytest.mark.parametrize("N", [64, 256, 8192])
@@ -211,7 +206,7 @@ def test_build_keeps_the_arithmetic_contract_and_the_engines_apart():
         code = re.sub(r"//.*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
         assert "csrc/" not in code and "asm" not in code and "atomic" not in code, name
         for inc in re.findall(r'#include "([^"]+)"', text):
-            assert inc in ("zen_hip.h", "zen_hip_tsm.h", "tsm_kernels.h", "wav.h", "../addon/addon_host.h"), (name, inc)
+            assert inc in ("zen_hip.h", "zen_hip_tsm.h", "tsm_kernels.h", "wav.h", "demo.h", "../addon/addon_host.h"), (name, inc)
     assert sorted(os.listdir(os.path.join(ROOT, "zen_amd", "addon"))) == ["addon_host.h", "hpri_pair.h", "median_select.h", "row_walk.h", "stft_args.h", "stft_host.h", "stft_kernels.h"]
 
 

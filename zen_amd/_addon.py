@@ -1,4 +1,4 @@
-"""What the ctypes bindings of the add-on libraries (pcm.py, ragged.py, live.py, pitch.py) share: loading, the return-code
+"""What the ctypes bindings of the add-on libraries (one module per entry of addon_build.LIBRARIES but blockrun) share: loading, the return-code
 check and the profile getters.  No fallback: a missing library that cannot be built raises."""
 import ctypes as C
 import os
@@ -22,7 +22,7 @@ def load(name, symbols):
             if env_var in os.environ:
                 raise ImportError("%s does not exist" % so)
             from . import addon_build
-            addon_build.EVERY_LIBRARY[name].build()
+            addon_build.LIBRARIES[name].build()
         _zl.load()                      # the same libzen_hip.so for both bindings (found again beside this one by its rpath)
         L = C.CDLL(so)
         for sym, res, args in symbols:

@@ -1,6 +1,7 @@
 // addon_host.h -- what the host sources of the add-on libraries share (zen_amd/pcm, ragged, live, pitch and every add-on
 // since: each a library of its own on top of libzen_hip.so's C ABI, include/zen_hip.h): the thread's error message and the
-// macros that set it, the per-kernel profile, the counting allocator and the roll-back of a create function.  What the
+// macros that set it, the per-kernel profile, the counting allocator, the base of a handle that owns both with its stream
+// and its row copies, the bodies of the calls every library exports around it, and the roll-back of a create function.  What the
 // spectrogram add-ons share beyond that is stft_host.h and, on the device side, stft_kernels.h and median_select.h.
 //
 // Header-only, and everything in it has internal linkage (the anonymous namespace): the libraries are routinely loaded into
@@ -13,6 +14,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 #include "zen_hip.h"
@@ -151,6 +153,84 @@ inline int counted_malloc(DeviceTally* t, void** p, size_t bytes, const char* wh
 	t->device_bytes += bytes;
 	t->allocations += 1;
 	return ZEN_HIP_OK;
+}
+
+inline bool is_pow2(size_t v) { return v && !(v & (v - 1)); }
+
+// What a library's handle struct inherits: the stream its work goes to, what it has allocated, the profile of its K kernels,
+// and the copies between the caller's rows and its own.
+template <int K>
+struct Handle {
+	hipStream_t stream = nullptr;
+	DeviceTally mem;
+	Profiler<K> prof;
+
+	template <class T>
+	int alloc(T** p, size_t count)
+	{
+		return counted_malloc(&mem, (void**)p, sizeof(T) * count, "zen_hip_malloc((void**)p, sizeof(T) * count)");
+	}
+
+	// `rows` rows of `cnt` floats between host and device memory, as one two-dimensional copy
+	int copy_rows(void* dst, size_t dst_stride, const void* src, size_t src_stride, size_t cnt, size_t rows, hipMemcpyKind kind)
+	{
+		if (cnt)
+			ZA_HIP_AS(hipMemcpy2DAsync(dst, sizeof(float) * dst_stride, src, sizeof(float) * src_stride, sizeof(float) * cnt, rows, kind, stream),
+			          "hipMemcpy2DAsync(dst, sizeof(float) * dst_stride, src, sizeof(float) * src_stride, sizeof(float) * cnt, rows, kind, h->stream)");
+		return ZEN_HIP_OK;
+	}
+
+	// The same rows as one-dimensional copies, for callers whose rows are long and few: one copy where both sides are
+	// tight, one per row otherwise.  No two-dimensional copy crosses the link.
+	int copy_rows_1d(float* dst, size_t dst_stride, const float* src, size_t src_stride, size_t cnt, size_t rows, hipMemcpyKind kind)
+	{
+		if (dst_stride == cnt && src_stride == cnt) {
+			ZA_HIP_AS(hipMemcpyAsync(dst, src, sizeof(float) * cnt * rows, kind, stream),
+			          "hipMemcpyAsync(dst, src, sizeof(float) * cnt * rows, kind, h->stream)");
+			return ZEN_HIP_OK;
+		}
+		for (size_t r = 0; r < rows; ++r)
+			ZA_HIP_AS(hipMemcpyAsync(dst + r * dst_stride, src + r * src_stride, sizeof(float) * cnt, kind, stream),
+			          "hipMemcpyAsync(dst + r * dst_stride, src + r * src_stride, sizeof(float) * cnt, kind, h->stream)");
+		return ZEN_HIP_OK;
+	}
+
+	// the tail of a destroy function, behind the wait for the stream: these buffers go, and the events never drained
+	void release(std::initializer_list<void*> bufs)
+	{
+		for (void* b : bufs)
+			(void)zen_hip_free(b);
+		prof.release();
+	}
+};
+
+// The bodies of three functions every library exports; `h` is whatever the caller handed in, null included, and `name` the
+// library's, for the message.
+template <class H>
+int set_stream(H* h, void* stream, const char* name)
+{
+	if (!h)
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s_set_stream: null handle", name);
+	ZA_HIP_AS(hipStreamSynchronize(h->stream), "hipStreamSynchronize(h->stream)");
+	h->stream = (hipStream_t)stream;
+	return ZEN_HIP_OK;
+}
+
+template <class H>
+int profile(H* h, int enable)
+{
+	if (!h)
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
+	h->prof.on = enable != 0;
+	return ZEN_HIP_OK;
+}
+
+template <class H>
+int profile_get(H* h, double* ms, unsigned long long* bytes, unsigned long long* launches, const char* name)
+{
+	if (!h || !ms || !bytes || !launches)
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s_profile_get: null argument", name);
+	return h->prof.drain(ms, bytes, launches);
 }
 
 // The second half of a create function: where `build` fails, `destroy` takes the half-built handle apart, and the message

@@ -12,7 +12,6 @@
 namespace zen_addon {
 namespace {
 
-inline bool is_pow2(size_t v) { return v && !(v & (v - 1)); }
 inline bool frame_ok(size_t nfft) { return is_pow2(nfft) && nfft >= 64 && nfft <= 8192; }
 inline size_t frames_of(size_t n, size_t H) { return (n + H - 1) / H + 1; }
 inline float window_at(size_t i, size_t N) { return (float)(0.54 - 0.46 * cos(2.0 * M_PI * (double)i / (double)N)); }

@@ -1,6 +1,6 @@
 """Builds the add-on libraries for gfx950 with hipcc: zen_amd/libzen_hip_<name>.so from zen_amd/<name>/, each a library of
-its own on top of libzen_hip.so's C ABI (blockrun: on top of the engine's state as well), and the demo programs zen_amd/bin/pitch-track, zen_amd/bin/beat-track,
-zen_amd/bin/zen-stems, zen_amd/bin/zen-repet, zen_amd/bin/zen-cqt, zen_amd/bin/zen-repsim, zen_amd/bin/zen-nmf, zen_amd/bin/zen-stretch and zen_amd/bin/zen-shift (plain g++: they reach the GPU through C ABIs only).
+its own on top of libzen_hip.so's C ABI (blockrun: on top of the engine's state as well), and the demo programs zen_amd/bin/<program>
+of the libraries that have one (plain g++: they reach the GPU through C ABIs only).  LIBRARIES, at the end, is the table of them.
 
     python zen_amd/addon_build.py [name ...] [--force]         # no name: all of them
 
@@ -25,10 +25,13 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 
 class Addon:
     """One add-on: zen_amd/<name>/<sources> -> zen_amd/build_<name>/*.o -> zen_amd/libzen_hip_<name>.so.  `extra_deps`: files
-    outside its directory whose change makes its objects stale; `build_demo`: a step behind the link."""
+    outside its directory whose change makes its objects stale; `demo`: (source, program, further add-ons it links) of the
+    program zen_amd/bin/<program>, a step behind the link -- DEMO is its path, None where the library has no program."""
 
-    def __init__(self, name, sources, extra_deps=(), build_demo=None, title=None, file_flags=None):
-        self.name, self.SOURCES, self.build_demo, self.title = name, list(sources), build_demo, title or name
+    def __init__(self, name, sources, extra_deps=(), demo=None, title=None, file_flags=None):
+        self.name, self.SOURCES, self.title = name, list(sources), title or name
+        self.demo_source, exe, self.demo_links = demo or (None, None, ())
+        self.DEMO = exe and os.path.join(HERE, "bin", exe)
         self.SRC = os.path.join(HERE, name)
         self.OUT = os.path.join(HERE, "libzen_hip_%s.so" % name)
         self.OBJDIR = os.path.join(HERE, "build_" + name)
@@ -70,87 +73,39 @@ class Addon:
                                   + ["-L", HERE, "-lzen_hip", "-Wl,-rpath,$ORIGIN"])
             if verbose:
                 print("built", self.OUT)
-        if self.build_demo:
+        if self.DEMO:
             self.build_demo(verbose)
         return self.OUT
 
-
-def _build_demo(name, source, exe, verbose, extra=()):
-    """zen_amd/bin/<exe> from zen_amd/<name>/<source>, against libzen_hip_<name>.so and libzen_hip.so; made again where the
-    source, the library's header, cli/wav.h or the library is newer.  `extra`: further add-ons whose libraries the program
-    links and whose headers it sees (they are built first where they are absent)."""
-    src, out = os.path.join(HERE, name), os.path.join(HERE, "libzen_hip_%s.so" % name)
-    srcs = [os.path.join(src, source), os.path.join(src, "zen_hip_%s.h" % name), os.path.join(HERE, "cli", "wav.h"), out]
-    more, libs = [], []
-    for e in extra:
-        if not os.path.exists(EVERY_LIBRARY[e].OUT):
-            EVERY_LIBRARY[e].build(verbose=verbose)
-        srcs += [os.path.join(HERE, e, "zen_hip_%s.h" % e), EVERY_LIBRARY[e].OUT]
-        more += ["-I", os.path.join(HERE, e)]
-        libs.append("-lzen_hip_" + e)
-    if os.path.exists(exe) and os.path.getmtime(exe) >= max(os.path.getmtime(p) for p in srcs):
+    def build_demo(self, verbose=False):
+        """zen_amd/bin/<program> from the add-on's demo source, against its library and libzen_hip.so; made again where the
+        source, the library's header, cli/wav.h, cli/demo.h or the library is newer.  The further add-ons it links are built
+        first where they are absent; it sees their headers too."""
+        name, exe = self.name, self.DEMO
+        srcs = [os.path.join(self.SRC, self.demo_source), os.path.join(self.SRC, "zen_hip_%s.h" % name), os.path.join(HERE, "cli", "wav.h"),
+                os.path.join(HERE, "cli", "demo.h"), self.OUT]
+        more, libs = [], []
+        for e in self.demo_links:
+            if not os.path.exists(LIBRARIES[e].OUT):
+                LIBRARIES[e].build(verbose=verbose)
+            srcs += [os.path.join(HERE, e, "zen_hip_%s.h" % e), LIBRARIES[e].OUT]
+            more += ["-I", os.path.join(HERE, e)]
+            libs.append("-lzen_hip_" + e)
+        if os.path.exists(exe) and os.path.getmtime(exe) >= max(os.path.getmtime(p) for p in srcs):
+            return exe
+        os.makedirs(os.path.dirname(exe), exist_ok=True)
+        subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
+                               "-I", self.SRC, "-I", os.path.join(HERE, "cli")] + more + [srcs[0], "-o", exe, "-L", HERE, "-lzen_hip_" + name] + libs
+                              + ["-lzen_hip", "-Wl,-rpath,$ORIGIN/.."])
+        if verbose:
+            print("built", exe)
         return exe
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
-                           "-I", src, "-I", os.path.join(HERE, "cli")] + more + [srcs[0], "-o", exe, "-L", HERE, "-lzen_hip_" + name] + libs
-                          + ["-lzen_hip", "-Wl,-rpath,$ORIGIN/.."])
-    if verbose:
-        print("built", exe)
-    return exe
-
-
-DEMO = os.path.join(HERE, "bin", "pitch-track")
-BEAT_DEMO = os.path.join(HERE, "bin", "beat-track")
-STEMS_DEMO = os.path.join(HERE, "bin", "zen-stems")
-REPET_DEMO = os.path.join(HERE, "bin", "zen-repet")
-CQT_DEMO = os.path.join(HERE, "bin", "zen-cqt")
-REPSIM_DEMO = os.path.join(HERE, "bin", "zen-repsim")
-NMF_DEMO = os.path.join(HERE, "bin", "zen-nmf")
-STRETCH_DEMO = os.path.join(HERE, "bin", "zen-stretch")
-SHIFT_DEMO = os.path.join(HERE, "bin", "zen-shift")
-
-
-def build_demo(verbose=False):
-    return _build_demo("pitch", "pitch_track.cpp", DEMO, verbose)
-
-
-def build_beat_demo(verbose=False):
-    return _build_demo("beat", "beat_track.cpp", BEAT_DEMO, verbose)
-
-
-def build_stems_demo(verbose=False):
-    return _build_demo("multi", "multi_stems.cpp", STEMS_DEMO, verbose)
-
-
-def build_repet_demo(verbose=False):
-    return _build_demo("repet", "repet_main.cpp", REPET_DEMO, verbose)
-
-
-def build_cqt_demo(verbose=False):
-    return _build_demo("cqt", "cqt_main.cpp", CQT_DEMO, verbose)
-
-
-def build_repsim_demo(verbose=False):
-    return _build_demo("repsim", "repsim_main.cpp", REPSIM_DEMO, verbose)
-
-
-def build_nmf_demo(verbose=False):
-    return _build_demo("nmf", "nmf_main.cpp", NMF_DEMO, verbose)
-
-
-def build_stretch_demo(verbose=False):
-    return _build_demo("tsm", "tsm_main.cpp", STRETCH_DEMO, verbose)
-
-
-def build_shift_demo(verbose=False):
-    return _build_demo("resample", "resample_main.cpp", SHIFT_DEMO, verbose, extra=("tsm",))
 
 
 pcm = Addon("pcm", ["pcm_kernels.hip", "pcm_pipe.hip"], extra_deps=["csrc/host_pipe.h"], title="PCM")
 ragged = Addon("ragged", ["ragged_kernels.hip", "ragged.hip"])
 live = Addon("live", ["live_kernels.hip", "live.hip"])
-pitch = Addon("pitch", ["pitch_kernels.hip", "pitch.hip"], build_demo=build_demo)
-ADDONS = {a.name: a for a in (pcm, ragged, live, pitch)}   # on the C ABI alone
+pitch = Addon("pitch", ["pitch_kernels.hip", "pitch.hip"], demo=("pitch_track.cpp", "pitch-track", ()))
 # blockrun shares the engine's state with libzen_hip.so at compile time (csrc/hpr_engine.h) and compiles the fused kernel's
 # headers into a kernel of its own: the csrc headers it includes make its objects stale, and its kernel file gets the
 # scheduler flags build.py gives rt_fused.hip, plus fft_dev.h's LDS-only barrier between the passes of a transform (a run
@@ -161,40 +116,22 @@ blockrun = Addon("blockrun", ["blockrun_kernel.hip", "blockrun.hip"],
                              "csrc/fft_dev.h", "csrc/median47_core.h", "csrc/median_net.h"],
                  file_flags={"blockrun_kernel.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-mllvm", "-amdgpu-use-amdgpu-trackers=1",
                                                      "-DZEN_FFT_LDS_BARRIER", "-DZEN_FFT_FOLD_ADDR", "-Wno-unused-function"]})
-ENGINE_ADDONS = {blockrun.name: blockrun}                  # on the engine's own state
-# beat came after the four of ADDONS and is, like them, on the C ABI alone; beat_track.cpp is the demo's, not the library's
-beat = Addon("beat", ["beat_kernels.hip", "beat.hip"], build_demo=build_beat_demo)
-# multi (interleaved multichannel audio through the engines' rows) shares the sample arithmetic of pcm/pcm_convert.h;
-# multi_stems.cpp is the demo's, not the library's
-multi = Addon("multi", ["multi_kernels.hip", "multi.hip"], extra_deps=["pcm/pcm_convert.h"], build_demo=build_stems_demo)
-# repet (repeating background against foreground) is on the C ABI alone as well; repet_main.cpp is the demo's, not the library's
-repet = Addon("repet", ["repet_kernels.hip", "repet.hip"], build_demo=build_repet_demo)
-# cqt (a sliced constant-Q transform and the separation in its domain) is on the C ABI alone too; cqt_main.cpp is the demo's
-cqt = Addon("cqt", ["cqt_kernels.hip", "cqt.hip"], build_demo=build_cqt_demo)
-# repsim (REPET-SIM: the repeating background found from the similarity matrix, the tree's one matrix-core kernel) is on the C
-# ABI alone as well; repsim_main.cpp is the demo's
-repsim = Addon("repsim", ["repsim_kernels.hip", "repsim.hip"], build_demo=build_repsim_demo)
-LATER_ADDONS = {beat.name: beat, multi.name: multi, repet.name: repet, cqt.name: cqt, repsim.name: repsim}
-# nmf (supervised factorisation of the magnitude spectrogram: three matrix products per iteration on the matrix cores) came
-# after the five of LATER_ADDONS and is, like them, on the C ABI alone; nmf_main.cpp is the demo's
-nmf = Addon("nmf", ["nmf_kernels.hip", "nmf.hip"], build_demo=build_nmf_demo)
-FACTOR_ADDONS = {nmf.name: nmf}
-ALL_ADDONS = {**ADDONS, **ENGINE_ADDONS, **LATER_ADDONS, **FACTOR_ADDONS}
-# tsm (time-scale modification: the harmonic stem through a phase-locked vocoder, the percussive one through overlap-add) is on
-# the C ABI alone as well; tsm_main.cpp is the demo's.  It has a table of its own: the eleven of ALL_ADDONS are the ones from
-# before it, and EVERY_ADDON is the lookup of the loader and of the command line.
-tsm = Addon("tsm", ["tsm_kernels.hip", "tsm.hip"], build_demo=build_stretch_demo)
-STRETCH_ADDONS = {tsm.name: tsm}
-EVERY_ADDON = {**ALL_ADDONS, **STRETCH_ADDONS}
-# resample (band-limited rate conversion by a rational ratio, and with tsm in front the pitch shift) is on the C ABI alone as
-# well; resample_main.cpp is the demo's, and links tsm's library too.  It has a table of its own again: EVERY_ADDON stays the
-# twelve from before it, and EVERY_LIBRARY is the lookup of the loader and of the command line.
-resample = Addon("resample", ["resample_kernels.hip", "resample.hip"], build_demo=build_shift_demo)
-SHIFT_ADDONS = {resample.name: resample}
-EVERY_LIBRARY = {**EVERY_ADDON, **SHIFT_ADDONS}
+beat = Addon("beat", ["beat_kernels.hip", "beat.hip"], demo=("beat_track.cpp", "beat-track", ()))
+# multi (interleaved multichannel audio through the engines' rows) shares the sample arithmetic of pcm/pcm_convert.h
+multi = Addon("multi", ["multi_kernels.hip", "multi.hip"], extra_deps=["pcm/pcm_convert.h"], demo=("multi_stems.cpp", "zen-stems", ()))
+repet = Addon("repet", ["repet_kernels.hip", "repet.hip"], demo=("repet_main.cpp", "zen-repet", ()))
+cqt = Addon("cqt", ["cqt_kernels.hip", "cqt.hip"], demo=("cqt_main.cpp", "zen-cqt", ()))
+repsim = Addon("repsim", ["repsim_kernels.hip", "repsim.hip"], demo=("repsim_main.cpp", "zen-repsim", ()))
+nmf = Addon("nmf", ["nmf_kernels.hip", "nmf.hip"], demo=("nmf_main.cpp", "zen-nmf", ()))
+tsm = Addon("tsm", ["tsm_kernels.hip", "tsm.hip"], demo=("tsm_main.cpp", "zen-stretch", ()))
+# zen-shift stretches with tsm's library before it resamples
+resample = Addon("resample", ["resample_kernels.hip", "resample.hip"], demo=("resample_main.cpp", "zen-shift", ("tsm",)))
+# The one table: every library by name, in the order they are built.  The loader (_addon.load), the programs' further
+# add-ons and the command line look names up here; blockrun alone is on the engine's own state, the rest on the C ABI alone.
+LIBRARIES = {a.name: a for a in (pcm, ragged, live, pitch, blockrun, beat, multi, repet, cqt, repsim, nmf, tsm, resample)}
 
 
 if __name__ == "__main__":
-    names = [a for a in sys.argv[1:] if not a.startswith("--")] or list(EVERY_LIBRARY)
+    names = [a for a in sys.argv[1:] if not a.startswith("--")] or list(LIBRARIES)
     for n in names:
-        EVERY_LIBRARY[n].build(force="--force" in sys.argv, verbose=True)
+        LIBRARIES[n].build(force="--force" in sys.argv, verbose=True)

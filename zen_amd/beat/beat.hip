@@ -29,12 +29,11 @@ enum { K_FRAME = 0, K_FFT = 1, K_CSD = 2, K_TRACK = 3, K_COUNT = ZEN_HIP_BEAT_KE
 
 } // namespace
 
-struct zen_hip_beat {
+struct zen_hip_beat : Handle<K_COUNT> {
 	float fs = 0.f;
 	size_t hop = 0, S = 0, max_hops = 0;
 	int bp[zen_beat::TEMPI] = {};
 	zen_hip_fft_t fft = nullptr; // 2 hop points
-	hipStream_t stream = nullptr;
 	float* rows = nullptr;     // (max_hops + 2) groups of S rows of 2 hop complex values
 	float* tail = nullptr;     // S rows of hop samples: the hop in front of the next call
 	float* odf = nullptr;      // S rows of max_hops onset values
@@ -44,17 +43,9 @@ struct zen_hip_beat {
 	float* stage_out[4] = {nullptr, nullptr, nullptr, nullptr}; // S rows of max_hops results
 	std::vector<float> state0; // the state of a fresh session (reset copies it up: it must outlive the copy)
 	unsigned long long hops = 0, slices = 0;
-	DeviceTally mem;
-	Profiler<K_COUNT> prof;
 };
 
 namespace {
-
-template <class T>
-int alloc(zen_hip_beat* h, T** p, size_t count)
-{
-	return counted_malloc(&h->mem, (void**)p, sizeof(T) * count, "zen_hip_malloc((void**)p, sizeof(T) * count)");
-}
 
 size_t group_floats(const zen_hip_beat* h) { return h->S * 4 * h->hop; }
 
@@ -126,9 +117,7 @@ int check_rows(const char* who, zen_hip_beat_t h, const void* in, size_t in_stri
 // rows of `cnt` floats between host and device memory
 int copy_rows(zen_hip_beat* h, void* dst, size_t dst_stride, const void* src, size_t src_stride, size_t cnt, hipMemcpyKind kind)
 {
-	if (cnt)
-		ZA_HIP(hipMemcpy2DAsync(dst, sizeof(float) * dst_stride, src, sizeof(float) * src_stride, sizeof(float) * cnt, h->S, kind, h->stream));
-	return ZEN_HIP_OK;
+	return h->copy_rows(dst, dst_stride, src, src_stride, cnt, h->S, kind);
 }
 
 // df = 1 at the multiples of the first period, cs = 0, prev = 1 | b, m0, bc, j, head
@@ -187,14 +176,14 @@ int zen_hip_beat_create(float fs, size_t hop, size_t n_streams, size_t max_hops,
 		const std::vector<float> tab = zen_beat::device_tables(fs, hop, bp);
 		h->state0 = fresh_state(h);
 		ZA_ZEN(zen_hip_fft_create(2 * hop, &h->fft));
-		ZA_TRY(alloc(h, &h->rows, (max_hops + 2) * group_floats(h)));
-		ZA_TRY(alloc(h, &h->tail, n_streams * hop));
-		ZA_TRY(alloc(h, &h->odf, rows));
-		ZA_TRY(alloc(h, &h->tables, tab.size()));
-		ZA_TRY(alloc(h, &h->state, h->state0.size()));
-		ZA_TRY(alloc(h, &h->stage_in, rows * hop));
+		ZA_TRY(h->alloc(&h->rows, (max_hops + 2) * group_floats(h)));
+		ZA_TRY(h->alloc(&h->tail, n_streams * hop));
+		ZA_TRY(h->alloc(&h->odf, rows));
+		ZA_TRY(h->alloc(&h->tables, tab.size()));
+		ZA_TRY(h->alloc(&h->state, h->state0.size()));
+		ZA_TRY(h->alloc(&h->stage_in, rows * hop));
 		for (float*& p : h->stage_out)
-			ZA_TRY(alloc(h, &p, rows));
+			ZA_TRY(h->alloc(&p, rows));
 		ZA_ZEN(zen_hip_memcpy_h2d(h->tables, tab.data(), sizeof(float) * tab.size()));
 		// whatever the transform allocates for its largest batch, up front: one run on zeros
 		ZA_HIP(hipMemsetAsync(h->rows, 0, sizeof(float) * (max_hops + 2) * group_floats(h), h->stream));
@@ -214,10 +203,7 @@ int zen_hip_beat_destroy(zen_hip_beat_t h)
 		return ZEN_HIP_OK;
 	(void)hipStreamSynchronize(h->stream);
 	zen_hip_fft_destroy(h->fft);
-	void* bufs[] = {h->rows, h->tail, h->odf, h->tables, h->state, h->stage_in, h->stage_out[0], h->stage_out[1], h->stage_out[2], h->stage_out[3]};
-	for (void* b : bufs)
-		(void)zen_hip_free(b);
-	h->prof.release();
+	h->release({h->rows, h->tail, h->odf, h->tables, h->state, h->stage_in, h->stage_out[0], h->stage_out[1], h->stage_out[2], h->stage_out[3]});
 	delete h;
 	return ZEN_HIP_OK;
 }
@@ -229,14 +215,7 @@ int zen_hip_beat_reset(zen_hip_beat_t h)
 	return reset(h);
 }
 
-int zen_hip_beat_set_stream(zen_hip_beat_t h, void* stream)
-{
-	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "beat_set_stream: null handle");
-	ZA_HIP(hipStreamSynchronize(h->stream));
-	h->stream = (hipStream_t)stream;
-	return ZEN_HIP_OK;
-}
+int zen_hip_beat_set_stream(zen_hip_beat_t h, void* stream) { return set_stream(h, stream, "beat"); }
 
 int zen_hip_beat_run_device(zen_hip_beat_t h, const float* in_dev, size_t in_stride, size_t n_hops, float* odf_dev, float* score_dev,
                             float* beat_dev, float* tempo_dev, size_t out_stride)
@@ -285,20 +264,12 @@ int zen_hip_beat_stats(zen_hip_beat_t h, zen_hip_beat_stats_t* out)
 	return ZEN_HIP_OK;
 }
 
-int zen_hip_beat_profile(zen_hip_beat_t h, int enable)
-{
-	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
-	h->prof.on = enable != 0;
-	return ZEN_HIP_OK;
-}
+int zen_hip_beat_profile(zen_hip_beat_t h, int enable) { return profile(h, enable); }
 
 int zen_hip_beat_profile_get(zen_hip_beat_t h, double ms[ZEN_HIP_BEAT_KERNELS], unsigned long long bytes[ZEN_HIP_BEAT_KERNELS],
                              unsigned long long launches[ZEN_HIP_BEAT_KERNELS])
 {
-	if (!h || !ms || !bytes || !launches)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "beat_profile_get: null argument");
-	return h->prof.drain(ms, bytes, launches);
+	return profile_get(h, ms, bytes, launches, "beat");
 }
 
 int zen_hip_beat_table(float fs, size_t hop, int which, size_t index, float* out, size_t cap)

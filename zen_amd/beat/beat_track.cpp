@@ -14,19 +14,16 @@
 #include <string>
 #include <vector>
 
+#include "demo.h"
 #include "wav.h"
 #include "zen_hip.h"
 #include "zen_hip_beat.h"
 
+using zen::demo::option;
+
 namespace {
 
-void check(int rc, const char* what, const char* msg)
-{
-	if (rc != ZEN_HIP_OK)
-		throw std::runtime_error(std::string(what) + ": " + msg);
-}
-#define ZEN(call) check((call), #call, zen_hip_last_error())
-#define BEAT(call) check((call), #call, zen_hip_beat_last_error())
+#define BEAT(call) ZEN_LIB(zen_hip_beat_last_error, call)
 
 int usage()
 {
@@ -52,18 +49,14 @@ int main(int argc, char** argv)
 	size_t hop = 512, hpr_hop = 1024;
 	float beta = 2.5f;
 	for (int i = 1; i < argc; ++i) {
-		char* end = nullptr;
 		if (!strcmp(argv[i], "--hop") && i + 1 < argc) {
-			hop = (size_t)strtoull(argv[++i], &end, 10);
-			if (*end)
+			if (!option(argv[++i], &hop))
 				return usage();
 		} else if (!strcmp(argv[i], "--hpr-hop") && i + 1 < argc) {
-			hpr_hop = (size_t)strtoull(argv[++i], &end, 10);
-			if (*end)
+			if (!option(argv[++i], &hpr_hop))
 				return usage();
 		} else if (!strcmp(argv[i], "--beta") && i + 1 < argc) {
-			beta = strtof(argv[++i], &end);
-			if (*end)
+			if (!option(argv[++i], &beta))
 				return usage();
 		} else if (argv[i][0] == '-' || !infile.empty()) {
 			return usage();
@@ -76,22 +69,14 @@ int main(int argc, char** argv)
 	zen_hip_hpr_t hpr = nullptr;
 	zen_hip_beat_t bt = nullptr;
 	float *dev = nullptr, *out = nullptr;
-	int status = 0;
-	try {
-		zen::wav::AudioData fd;
-		zen::wav::load(fd, infile);
-		std::vector<float> mono;
-		if (fd.channelCount == 2) {
-			mono.resize(fd.samples.size() / 2);
-			zen::wav::stereo_to_mono(fd.samples.data(), mono.data(), fd.samples.size());
-		} else {
-			mono = fd.samples;
-		}
+	const auto body = [&] {
+		int rate = 0;
+		std::vector<float> mono = zen::demo::load_mono(infile, &rate);
 		const size_t unit = hop > hpr_hop ? hop : hpr_hop;
 		if (unit % hop || unit % hpr_hop)
 			throw std::runtime_error("one hop must be a multiple of the other");
 		const size_t len = mono.size() / unit * unit, n_hops = len / hop;
-		const float fs = (float)fd.sampleRate;
+		const float fs = (float)rate;
 		ZEN(zen_hip_init(0));
 		BEAT(zen_hip_beat_create(fs, hop, 2, 0, &bt)); // stream 0: the recording, stream 1: its percussive part
 		ZEN(zen_hip_hpr_create(fs, hpr_hop, beta, ZEN_HIP_OUTPUT_PERCUSSIVE, ZEN_HIP_TIME_CAUSAL, 1, 1, 0, &hpr));
@@ -106,20 +91,11 @@ int main(int argc, char** argv)
 		}
 		print_beats("+HPR", beat.data() + n_hops, n_hops, hop, (double)fs);
 		print_beats("-HPR", beat.data(), n_hops, hop, (double)fs);
-	} catch (const std::exception& e) {
-		fprintf(stderr, "beat-track: %s\n", e.what());
-		status = 1;
-	}
-	zen_hip_beat_destroy(bt);
-	zen_hip_hpr_destroy(hpr);
-	zen_hip_free(dev);
-	zen_hip_free(out);
-	if (status == 0) { // as `zen`: a red zone found overwritten is an error of its own
-		zen_hip_memcheck_report rep;
-		if (zen_hip_memcheck(&rep) == ZEN_HIP_OK && rep.corrupt_words) {
-			fprintf(stderr, "beat-track: memory check: %s\n", rep.first_message);
-			status = 86;
-		}
-	}
-	return status;
+	};
+	return zen::demo::run("beat-track", body, [&] {
+		zen_hip_beat_destroy(bt);
+		zen_hip_hpr_destroy(hpr);
+		zen_hip_free(dev);
+		zen_hip_free(out);
+	});
 }

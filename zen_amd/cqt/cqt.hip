@@ -30,7 +30,6 @@ static_assert(K_COUNT == ZEN_HIP_CQT_KERNELS, "the header names the kernels");
 constexpr int WMIN = 4;
 constexpr size_t RUN_BYTES = (size_t)32 << 20; // the per-stem scratch: as many slices as fit, one at the least
 
-bool is_pow2(size_t v) { return v && !(v & (v - 1)); }
 
 // The host side of the contract: the centres, M and the tables, all from doubles (libm cos and pow), rounded once.
 struct Plan {
@@ -123,14 +122,13 @@ void plan_tables(Plan* pl)
 
 } // namespace
 
-struct zen_hip_cqt {
+struct zen_hip_cqt : Handle<K_COUNT> {
 	Plan pl;
 	size_t C = 0, n = 0, ns = 0, T = 0, run = 0;
 	float beta = 2.0f;
 	int soft = 0, lh = 0, lp = 0, B = 0;
 	zen_hip_fft_t fft_slice = nullptr, fft_band = nullptr;
 	zen_hip_mfilt_t med_time = nullptr, med_freq = nullptr;
-	hipStream_t stream = nullptr;
 	float* rows = nullptr;    // C * ns rows of Ls complex values: the slice spectra, later Y_q of the stem at hand
 	float* coef = nullptr;    // C * ns * nb rows of M complex values: the one copy of the coefficients
 	float* scratch = nullptr; // run * nb rows of M complex values: the masked coefficients of the stem at hand
@@ -141,17 +139,9 @@ struct zen_hip_cqt {
 	float* stage_out[3] = {nullptr, nullptr, nullptr};
 	zen_cqt::Tables tab = {};
 	unsigned long long calls = 0, clips = 0;
-	DeviceTally mem;
-	Profiler<K_COUNT> prof;
 };
 
 namespace {
-
-template <class T>
-int alloc(zen_hip_cqt* h, T** p, size_t count)
-{
-	return counted_malloc(&h->mem, (void**)p, sizeof(T) * count, "zen_hip_malloc((void**)p, sizeof(T) * count)");
-}
 
 void default_lengths(const zen_hip_cqt* h, int* lh, int* lp)
 {
@@ -345,8 +335,7 @@ int separate(zen_hip_cqt* h, const float* in, size_t in_stride, float* const out
 // rows of `cnt` floats between host and device memory
 int copy_rows(zen_hip_cqt* h, void* dst, size_t dst_stride, const void* src, size_t src_stride, size_t cnt, hipMemcpyKind kind)
 {
-	ZA_HIP(hipMemcpy2DAsync(dst, sizeof(float) * dst_stride, src, sizeof(float) * src_stride, sizeof(float) * cnt, h->C, kind, h->stream));
-	return ZEN_HIP_OK;
+	return h->copy_rows(dst, dst_stride, src, src_stride, cnt, h->C, kind);
 }
 
 } // namespace
@@ -426,17 +415,17 @@ int zen_hip_cqt_create(float fs, size_t slice, int bands_per_octave, double fmin
 		ZA_ZEN(zen_hip_fft_create(Ls, &h->fft_slice));
 		ZA_ZEN(zen_hip_fft_create(M, &h->fft_band));
 		const size_t rows = n_clips * ns;
-		ZA_TRY(alloc(h, &h->rows, rows * 2 * Ls));
-		ZA_TRY(alloc(h, &h->coef, rows * nb * M * 2));
-		ZA_TRY(alloc(h, &h->scratch, h->run * nb * M * 2));
-		ZA_TRY(alloc(h, &h->v, T * nb));
-		ZA_TRY(alloc(h, &h->hm, T * nb));
-		ZA_TRY(alloc(h, &h->pm, T * nb));
-		ZA_TRY(alloc(h, &h->ftab, 4 * (N + 1) + 2 * Ls));
-		ZA_TRY(alloc(h, &h->itab, N + 1 + nb));
-		ZA_TRY(alloc(h, &h->stage_in, n_clips * n_samples));
+		ZA_TRY(h->alloc(&h->rows, rows * 2 * Ls));
+		ZA_TRY(h->alloc(&h->coef, rows * nb * M * 2));
+		ZA_TRY(h->alloc(&h->scratch, h->run * nb * M * 2));
+		ZA_TRY(h->alloc(&h->v, T * nb));
+		ZA_TRY(h->alloc(&h->hm, T * nb));
+		ZA_TRY(h->alloc(&h->pm, T * nb));
+		ZA_TRY(h->alloc(&h->ftab, 4 * (N + 1) + 2 * Ls));
+		ZA_TRY(h->alloc(&h->itab, N + 1 + nb));
+		ZA_TRY(h->alloc(&h->stage_in, n_clips * n_samples));
 		for (float*& p : h->stage_out)
-			ZA_TRY(alloc(h, &p, n_clips * n_samples));
+			ZA_TRY(h->alloc(&p, n_clips * n_samples));
 		std::vector<float> ft;
 		for (const std::vector<float>* t : {&h->pl.gL, &h->pl.gU, &h->pl.gdL, &h->pl.gdU, &h->pl.h, &h->pl.s})
 			ft.insert(ft.end(), t->begin(), t->end());
@@ -472,22 +461,12 @@ int zen_hip_cqt_destroy(zen_hip_cqt_t h)
 	zen_hip_fft_destroy(h->fft_band);
 	zen_hip_mfilt_destroy(h->med_time);
 	zen_hip_mfilt_destroy(h->med_freq);
-	void* bufs[] = {h->rows, h->coef, h->scratch, h->v, h->hm, h->pm, h->ftab, h->itab, h->stage_in, h->stage_out[0], h->stage_out[1], h->stage_out[2]};
-	for (void* b : bufs)
-		(void)zen_hip_free(b);
-	h->prof.release();
+	h->release({h->rows, h->coef, h->scratch, h->v, h->hm, h->pm, h->ftab, h->itab, h->stage_in, h->stage_out[0], h->stage_out[1], h->stage_out[2]});
 	delete h;
 	return ZEN_HIP_OK;
 }
 
-int zen_hip_cqt_set_stream(zen_hip_cqt_t h, void* stream)
-{
-	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "cqt_set_stream: null handle");
-	ZA_HIP(hipStreamSynchronize(h->stream));
-	h->stream = (hipStream_t)stream;
-	return ZEN_HIP_OK;
-}
+int zen_hip_cqt_set_stream(zen_hip_cqt_t h, void* stream) { return set_stream(h, stream, "cqt"); }
 
 int zen_hip_cqt_set_params(zen_hip_cqt_t h, float beta, int soft, int lh, int lp)
 {
@@ -606,20 +585,12 @@ int zen_hip_cqt_stats(zen_hip_cqt_t h, zen_hip_cqt_stats_t* out)
 	return ZEN_HIP_OK;
 }
 
-int zen_hip_cqt_profile(zen_hip_cqt_t h, int enable)
-{
-	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
-	h->prof.on = enable != 0;
-	return ZEN_HIP_OK;
-}
+int zen_hip_cqt_profile(zen_hip_cqt_t h, int enable) { return profile(h, enable); }
 
 int zen_hip_cqt_profile_get(zen_hip_cqt_t h, double ms[ZEN_HIP_CQT_KERNELS], unsigned long long bytes[ZEN_HIP_CQT_KERNELS],
                             unsigned long long launches[ZEN_HIP_CQT_KERNELS])
 {
-	if (!h || !ms || !bytes || !launches)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "cqt_profile_get: null argument");
-	return h->prof.drain(ms, bytes, launches);
+	return profile_get(h, ms, bytes, launches, "cqt");
 }
 
 } // extern "C"

@@ -7,7 +7,6 @@
 // prefix_harm.wav, prefix_perc.wav and prefix_residual.wav are written as `zen offline` writes its stems: divided by the
 // stem's peak (a silent stem stays silent), 16-bit PCM with cli/wav.h's rounding.  The plan is printed first.  A recording of
 // more than 4096 slices is refused: the library has no streaming form of the transform.
-#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -16,19 +15,16 @@
 #include <string>
 #include <vector>
 
+#include "demo.h"
 #include "wav.h"
 #include "zen_hip.h"
 #include "zen_hip_cqt.h"
 
+using zen::demo::option;
+
 namespace {
 
-void check(int rc, const char* what, const char* msg)
-{
-	if (rc != ZEN_HIP_OK)
-		throw std::runtime_error(std::string(what) + ": " + msg);
-}
-#define ZEN(call) check((call), #call, zen_hip_last_error())
-#define CQT(call) check((call), #call, zen_hip_cqt_last_error())
+#define CQT(call) ZEN_LIB(zen_hip_cqt_last_error, call)
 
 int usage()
 {
@@ -37,16 +33,6 @@ int usage()
 	                "factor of the hard masks, from 1 on (default 2)\n  writes prefix_harm.wav, prefix_perc.wav and prefix_residual.wav; at most "
 	                "4096 slices of N / 2 samples\n");
 	return 2;
-}
-
-void peak_normalise(std::vector<float>& x) // as `zen offline`; a stem of zeros is left as it is
-{
-	auto limits = std::minmax_element(x.begin(), x.end());
-	const float real_max = std::max(-1 * (*limits.first), *limits.second);
-	if (!(real_max > 0.0f))
-		return;
-	for (float& v : x)
-		v /= real_max;
 }
 
 } // namespace
@@ -59,24 +45,19 @@ int main(int argc, char** argv)
 	double fmin = 60.0, beta = 2.0;
 	int soft = 0;
 	for (int i = 1; i < argc; ++i) {
-		char* end = nullptr;
 		if (!strcmp(argv[i], "-o") && i + 1 < argc) {
 			prefix = argv[++i];
 		} else if (!strcmp(argv[i], "--slice") && i + 1 < argc) {
-			slice = (size_t)strtoull(argv[++i], &end, 10);
-			if (*end)
+			if (!option(argv[++i], &slice))
 				return usage();
 		} else if (!strcmp(argv[i], "--bpo") && i + 1 < argc) {
-			bpo = strtol(argv[++i], &end, 10);
-			if (*end || bpo < 1 || bpo > 96)
+			if (!option(argv[++i], &bpo) || bpo < 1 || bpo > 96)
 				return usage();
 		} else if (!strcmp(argv[i], "--fmin") && i + 1 < argc) {
-			fmin = strtod(argv[++i], &end);
-			if (*end || !(fmin > 0.0))
+			if (!option(argv[++i], &fmin) || !(fmin > 0.0))
 				return usage();
 		} else if (!strcmp(argv[i], "--beta") && i + 1 < argc) {
-			beta = strtod(argv[++i], &end);
-			if (*end || !(beta >= 1.0))
+			if (!option(argv[++i], &beta) || !(beta >= 1.0))
 				return usage();
 		} else if (!strcmp(argv[i], "--soft-mask")) {
 			soft = 1;
@@ -90,21 +71,13 @@ int main(int argc, char** argv)
 		return usage();
 	zen_hip_cqt_t cq = nullptr;
 	float* dev = nullptr;
-	int status = 0;
-	try {
-		zen::wav::AudioData fd;
-		zen::wav::load(fd, infile);
-		std::vector<float> mono;
-		if (fd.channelCount == 2) {
-			mono.resize(fd.samples.size() / 2);
-			zen::wav::stereo_to_mono(fd.samples.data(), mono.data(), fd.samples.size());
-		} else {
-			mono = fd.samples;
-		}
+	const auto body = [&] {
+		int rate = 0;
+		std::vector<float> mono = zen::demo::load_mono(infile, &rate);
 		const size_t n = mono.size();
 		if (n == 0)
 			throw std::runtime_error("no samples in " + infile);
-		const float fs = (float)fd.sampleRate;
+		const float fs = (float)rate;
 		size_t nb = 0, m = 0;
 		CQT(zen_hip_cqt_plan(fs, slice, (int)bpo, fmin, &nb, &m, nullptr, 0));
 		printf("plan: %zu bands, %zu coefficients per band and slice, %.2f columns per second\n", nb, m, (double)fs * (double)m / (double)slice);
@@ -118,21 +91,12 @@ int main(int argc, char** argv)
 		std::vector<float> stem(n);
 		for (int o = 0; o < 3; ++o) {
 			ZEN(zen_hip_memcpy_d2h(stem.data(), dev + (size_t)(o + 1) * n, sizeof(float) * n));
-			peak_normalise(stem);
-			zen::wav::encode_pcm16_mono(stem, fd.sampleRate, prefix + suffix[o]);
+			zen::demo::peak_normalise(stem);
+			zen::wav::encode_pcm16_mono(stem, rate, prefix + suffix[o]);
 		}
-	} catch (const std::exception& e) {
-		fprintf(stderr, "zen-cqt: %s\n", e.what());
-		status = 1;
-	}
-	zen_hip_cqt_destroy(cq);
-	zen_hip_free(dev);
-	if (status == 0) { // as `zen`: a red zone found overwritten is an error of its own
-		zen_hip_memcheck_report rep;
-		if (zen_hip_memcheck(&rep) == ZEN_HIP_OK && rep.corrupt_words) {
-			fprintf(stderr, "zen-cqt: memory check: %s\n", rep.first_message);
-			status = 86;
-		}
-	}
-	return status;
+	};
+	return zen::demo::run("zen-cqt", body, [&] {
+		zen_hip_cqt_destroy(cq);
+		zen_hip_free(dev);
+	});
 }

@@ -39,9 +39,8 @@ unsigned long long max_samples(size_t hop_p) // zen_hip_live.h, "The bound"
 
 } // namespace
 
-struct zen_hip_live : HpriPair {
+struct zen_hip_live : HpriPair, Handle<3> {
 	size_t hop_h = 0, hop_p = 0, S = 0, sh1 = 0, sh2 = 0, max_push = 0;
-	hipStream_t stream = nullptr;
 	// rows per stream (floats): pass 1's largest slice, pass 2's, the most one call delivers, the history in front of H1
 	size_t cap1 = 0, cap2 = 0, ocap = 0, hoff = 0, row1 = 0, carry_row = 0, dry_len = 0;
 	float *carry[2] = {nullptr, nullptr}, *in1 = nullptr, *h1[2] = {nullptr, nullptr}, *p1 = nullptr, *r1 = nullptr, *in2 = nullptr,
@@ -51,8 +50,6 @@ struct zen_hip_live : HpriPair {
 	// the stream so far
 	unsigned long long pushed = 0, delivered = 0, limit = 0;
 	size_t c = 0; // samples in the carry: pushed % hop_h
-	DeviceTally mem;
-	Profiler<3> prof;
 };
 
 namespace {
@@ -237,9 +234,7 @@ int finish_device(zen_hip_live_t h, float* harm, float* perc, float* dry, size_t
 // rows of `cnt` floats between host memory (rows host_stride apart) and the staging rows (dev_stride apart)
 int copy_rows(zen_hip_live* h, void* dst, size_t dst_stride, const void* src, size_t src_stride, size_t cnt, hipMemcpyKind kind)
 {
-	if (cnt)
-		ZA_HIP(hipMemcpy2DAsync(dst, sizeof(float) * dst_stride, src, sizeof(float) * src_stride, sizeof(float) * cnt, h->S, kind, h->stream));
-	return ZEN_HIP_OK;
+	return h->copy_rows(dst, dst_stride, src, src_stride, cnt, h->S, kind);
 }
 
 } // namespace
@@ -323,11 +318,8 @@ int zen_hip_live_destroy(zen_hip_live_t h)
 		return ZEN_HIP_OK;
 	(void)hipStreamSynchronize(h->stream);
 	pair_destroy(h);
-	float* bufs[] = {h->carry[0], h->carry[1], h->in1, h->h1[0], h->h1[1], h->p1, h->r1, h->in2, h->p2, h->dry, h->stage_in,
-	                 h->stage_out[0], h->stage_out[1], h->stage_out[2]};
-	for (float* b : bufs)
-		(void)zen_hip_free(b);
-	h->prof.release();
+	h->release({h->carry[0], h->carry[1], h->in1, h->h1[0], h->h1[1], h->p1, h->r1, h->in2, h->p2, h->dry, h->stage_in, h->stage_out[0],
+	            h->stage_out[1], h->stage_out[2]});
 	delete h;
 	return ZEN_HIP_OK;
 }
@@ -484,9 +476,7 @@ int zen_hip_live_profile(zen_hip_live_t h, int enable)
 
 int zen_hip_live_profile_get(zen_hip_live_t h, double ms[3], unsigned long long bytes[3], unsigned long long launches[3])
 {
-	if (!h || !ms || !bytes || !launches)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "live_profile_get: null argument");
-	return h->prof.drain(ms, bytes, launches);
+	return profile_get(h, ms, bytes, launches, "live");
 }
 
 int zen_hip_live_profile_get_engine(zen_hip_live_t h, int pass, double ms[6], unsigned long long launches[6])

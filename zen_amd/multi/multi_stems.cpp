@@ -15,19 +15,14 @@
 #include <string>
 #include <vector>
 
+#include "demo.h"
 #include "wav.h"
 #include "zen_hip.h"
 #include "zen_hip_multi.h"
 
 namespace {
 
-void check(int rc, const char* what, const char* msg)
-{
-	if (rc != ZEN_HIP_OK)
-		throw std::runtime_error(std::string(what) + ": " + msg);
-}
-#define ZEN(call) check((call), #call, zen_hip_last_error())
-#define MULTI(call) check((call), #call, zen_hip_multi_last_error())
+#define MULTI(call) ZEN_LIB(zen_hip_multi_last_error, call)
 
 int usage()
 {
@@ -78,8 +73,7 @@ int main(int argc, char** argv)
 			prefix.resize(prefix.size() - 4);
 	}
 	zen_hip_multi_offline_t h = nullptr;
-	int status = 0;
-	try {
+	const auto body = [&] {
 		zen::wav::AudioData fd;
 		zen::wav::load(fd, infile);
 		if (fd.channelCount > ZEN_HIP_MULTI_MAX_CHANNELS)
@@ -106,17 +100,8 @@ int main(int argc, char** argv)
 		zen::wav::encode_pcm16_interleaved(perc, C, fd.sampleRate, prefix + "_perc.wav");
 		printf("%zu frames of %d channels at %d Hz -> %s_harm.wav (peak %g), %s_perc.wav (peak %g)\n", n_frames, C, fd.sampleRate, prefix.c_str(),
 		       (double)peaks[0], prefix.c_str(), (double)peaks[1]);
-	} catch (const std::exception& e) {
-		fprintf(stderr, "zen-stems: %s\n", e.what());
-		status = 1;
-	}
-	zen_hip_multi_offline_destroy(h);
-	if (status == 0) { // as `zen`: a red zone found overwritten is an error of its own
-		zen_hip_memcheck_report rep;
-		if (zen_hip_memcheck(&rep) == ZEN_HIP_OK && rep.corrupt_words) {
-			fprintf(stderr, "zen-stems: memory check: %s\n", rep.first_message);
-			status = 86;
-		}
-	}
-	return status;
+	};
+	return zen::demo::run("zen-stems", body, [&] {
+		zen_hip_multi_offline_destroy(h);
+	});
 }

@@ -38,12 +38,11 @@ constexpr bool DEFAULT_MFMA = true;
 
 } // namespace
 
-struct zen_hip_nmf {
+struct zen_hip_nmf : Handle<K_COUNT> {
 	float fs = 0.f;
 	size_t N = 0, H = 0, bins = 0, v_stride = 0, K = 0, C = 0, max_samples = 0, max_frames = 0;
 	bool mfma = DEFAULT_MFMA;
 	zen_hip_fft_t fft = nullptr; // N points
-	hipStream_t stream = nullptr;
 	float* rows = nullptr;      // C * max_frames rows of N complex values: X
 	float* masked = nullptr;    // max_frames rows of N complex values: one clip through one group's mask
 	float* v = nullptr;         // C * max_frames rows of v_stride floats
@@ -56,17 +55,9 @@ struct zen_hip_nmf {
 	float* part = nullptr;      // the segments' sums of a split update: part_floats floats, and K per segment behind them
 	size_t part_floats = 0;
 	unsigned long long calls = 0, clips = 0, iterations = 0;
-	DeviceTally mem;
-	Profiler<K_COUNT> prof;
 };
 
 namespace {
-
-template <class T>
-int alloc(zen_hip_nmf* h, T** p, size_t count)
-{
-	return counted_malloc(&h->mem, (void**)p, sizeof(T) * count, "zen_hip_malloc((void**)p, sizeof(T) * count)");
-}
 
 // steps 1-2 for every clip
 int spectra(zen_hip_nmf* h, const float* in, size_t in_stride, size_t n, size_t m)
@@ -193,12 +184,6 @@ int check_process(const char* who, zen_hip_nmf_t h, const void* in, size_t in_st
 }
 
 // rows of `cnt` floats between host and device memory
-int copy_rows(zen_hip_nmf* h, void* dst, size_t dst_stride, const void* src, size_t src_stride, size_t cnt, size_t rows, hipMemcpyKind kind)
-{
-	ZA_HIP(hipMemcpy2DAsync(dst, sizeof(float) * dst_stride, src, sizeof(float) * src_stride, sizeof(float) * cnt, rows, kind, h->stream));
-	return ZEN_HIP_OK;
-}
-
 int check_alone(const char* who, const void* const* ptrs, int count, size_t K, size_t F, size_t m, int route)
 {
 	for (int i = 0; i < count; ++i)
@@ -259,20 +244,20 @@ int zen_hip_nmf_create(float fs, size_t nfft, size_t components, size_t n_clips,
 		const size_t frames = n_clips * h->max_frames;
 		const std::vector<float> tab = stft_tables(nfft);
 		ZA_ZEN(zen_hip_fft_create(nfft, &h->fft));
-		ZA_TRY(alloc(h, &h->rows, frames * 2 * nfft));
-		ZA_TRY(alloc(h, &h->masked, h->max_frames * 2 * nfft));
-		ZA_TRY(alloc(h, &h->v, frames * h->v_stride));
-		ZA_TRY(alloc(h, &h->q, h->max_frames * h->v_stride));
-		ZA_TRY(alloc(h, &h->tables, tab.size()));
-		ZA_TRY(alloc(h, &h->stage_in, n_clips * max_samples));
-		ZA_TRY(alloc(h, &h->stage_out, n_clips * max_samples));
-		ZA_TRY(alloc(h, &h->stage_w, n_clips * components * h->v_stride));
-		ZA_TRY(alloc(h, &h->stage_h, n_clips * components * h->max_frames));
+		ZA_TRY(h->alloc(&h->rows, frames * 2 * nfft));
+		ZA_TRY(h->alloc(&h->masked, h->max_frames * 2 * nfft));
+		ZA_TRY(h->alloc(&h->v, frames * h->v_stride));
+		ZA_TRY(h->alloc(&h->q, h->max_frames * h->v_stride));
+		ZA_TRY(h->alloc(&h->tables, tab.size()));
+		ZA_TRY(h->alloc(&h->stage_in, n_clips * max_samples));
+		ZA_TRY(h->alloc(&h->stage_out, n_clips * max_samples));
+		ZA_TRY(h->alloc(&h->stage_w, n_clips * components * h->v_stride));
+		ZA_TRY(h->alloc(&h->stage_h, n_clips * components * h->max_frames));
 		// the larger of the two updates' segment sums, as far as SPLIT_BYTES go: a longer one walks its segments in sequence
 		const size_t need_h = segments_of(h->bins) * components * h->max_frames, need_w = segments_of(h->max_frames) * components * h->bins;
 		const size_t cap = ZEN_HIP_NMF_SPLIT_BYTES / sizeof(float);
 		h->part_floats = std::max(need_h <= cap ? need_h : 0, need_w <= cap ? need_w : 0);
-		ZA_TRY(alloc(h, &h->part, h->part_floats + (size_t)(ZEN_HIP_NMF_MAX_FRAMES / ZEN_HIP_NMF_SEGMENT) * components));
+		ZA_TRY(h->alloc(&h->part, h->part_floats + (size_t)(ZEN_HIP_NMF_MAX_FRAMES / ZEN_HIP_NMF_SEGMENT) * components));
 		ZA_ZEN(zen_hip_memcpy_h2d(h->tables, tab.data(), sizeof(float) * tab.size()));
 		// whatever the transform allocates for its largest batch, up front: one run on zeros
 		ZA_HIP(hipMemsetAsync(h->rows, 0, sizeof(float) * frames * 2 * nfft, h->stream));
@@ -291,22 +276,12 @@ int zen_hip_nmf_destroy(zen_hip_nmf_t h)
 		return ZEN_HIP_OK;
 	(void)hipStreamSynchronize(h->stream);
 	zen_hip_fft_destroy(h->fft);
-	void* bufs[] = {h->rows, h->masked, h->v, h->q, h->tables, h->stage_in, h->stage_out, h->stage_w, h->stage_h, h->part};
-	for (void* b : bufs)
-		(void)zen_hip_free(b);
-	h->prof.release();
+	h->release({h->rows, h->masked, h->v, h->q, h->tables, h->stage_in, h->stage_out, h->stage_w, h->stage_h, h->part});
 	delete h;
 	return ZEN_HIP_OK;
 }
 
-int zen_hip_nmf_set_stream(zen_hip_nmf_t h, void* stream)
-{
-	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "nmf_set_stream: null handle");
-	ZA_HIP(hipStreamSynchronize(h->stream));
-	h->stream = (hipStream_t)stream;
-	return ZEN_HIP_OK;
-}
+int zen_hip_nmf_set_stream(zen_hip_nmf_t h, void* stream) { return set_stream(h, stream, "nmf"); }
 
 int zen_hip_nmf_process_device(zen_hip_nmf_t h, const float* in_dev, size_t in_stride, size_t n, float* w_dev, size_t w_stride,
                                size_t w_clip_stride, float* h_dev, size_t h_stride, size_t h_clip_stride, size_t fixed, int iterations,
@@ -340,11 +315,11 @@ int zen_hip_nmf_process_host(zen_hip_nmf_t h, const float* in_host, size_t in_st
 	const size_t C = h->C, K = h->K, F = h->bins, m = frames_of(n, h->H), row = h->max_samples, ws = h->v_stride, hs = h->max_frames;
 	const size_t wcs = w_clip_stride ? K * ws : 0, hcs = K * hs, dicts = w_clip_stride ? C : 1;
 	auto run = [&]() -> int {
-		ZA_TRY(copy_rows(h, h->stage_in, row, in_host, in_stride, n, C, hipMemcpyHostToDevice));
+		ZA_TRY(h->copy_rows(h->stage_in, row, in_host, in_stride, n, C, hipMemcpyHostToDevice));
 		for (size_t c = 0; c < dicts; ++c)
-			ZA_TRY(copy_rows(h, h->stage_w + c * wcs, ws, w_host + c * w_clip_stride, w_stride, F, K, hipMemcpyHostToDevice));
+			ZA_TRY(h->copy_rows(h->stage_w + c * wcs, ws, w_host + c * w_clip_stride, w_stride, F, K, hipMemcpyHostToDevice));
 		for (size_t c = 0; c < C; ++c)
-			ZA_TRY(copy_rows(h, h->stage_h + c * hcs, hs, h_host + c * h_clip_stride, h_stride, m, K, hipMemcpyHostToDevice));
+			ZA_TRY(h->copy_rows(h->stage_h + c * hcs, hs, h_host + c * h_clip_stride, h_stride, m, K, hipMemcpyHostToDevice));
 		ZA_TRY(spectra(h, h->stage_in, row, n, m));
 		for (size_t c = 0; c < C; ++c) {
 			const Matrices x = {h->stage_w + c * wcs, h->stage_h + c * hcs, ws, hs};
@@ -352,17 +327,17 @@ int zen_hip_nmf_process_host(zen_hip_nmf_t h, const float* in_host, size_t in_st
 		}
 		if (fixed < K) // held spectra are what the caller has
 			for (size_t c = 0; c < dicts; ++c)
-				ZA_TRY(copy_rows(h, w_host + c * w_clip_stride + fixed * w_stride, w_stride, h->stage_w + c * wcs + fixed * ws, ws, F, K - fixed,
+				ZA_TRY(h->copy_rows(w_host + c * w_clip_stride + fixed * w_stride, w_stride, h->stage_w + c * wcs + fixed * ws, ws, F, K - fixed,
 				                 hipMemcpyDeviceToHost));
 		for (size_t c = 0; c < C; ++c)
-			ZA_TRY(copy_rows(h, h_host + c * h_clip_stride, h_stride, h->stage_h + c * hcs, hs, m, K, hipMemcpyDeviceToHost));
+			ZA_TRY(h->copy_rows(h_host + c * h_clip_stride, h_stride, h->stage_h + c * hcs, hs, m, K, hipMemcpyDeviceToHost));
 		if (groups_host)
 			for (size_t g = 0; g < n_groups; ++g) { // one group's rows at a time through the stage
 				for (size_t c = 0; c < C; ++c) {
 					const Matrices x = {h->stage_w + c * wcs, h->stage_h + c * hcs, ws, hs};
 					ZA_TRY(stem(h, c, n, m, x, groups_host, (int)g, h->stage_out + c * row));
 				}
-				ZA_TRY(copy_rows(h, stems_host + g * C * out_stride, out_stride, h->stage_out, row, n, C, hipMemcpyDeviceToHost));
+				ZA_TRY(h->copy_rows(stems_host + g * C * out_stride, out_stride, h->stage_out, row, n, C, hipMemcpyDeviceToHost));
 			}
 		return ZEN_HIP_OK;
 	};
@@ -438,20 +413,12 @@ int zen_hip_nmf_stats(zen_hip_nmf_t h, zen_hip_nmf_stats_t* out)
 	return ZEN_HIP_OK;
 }
 
-int zen_hip_nmf_profile(zen_hip_nmf_t h, int enable)
-{
-	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
-	h->prof.on = enable != 0;
-	return ZEN_HIP_OK;
-}
+int zen_hip_nmf_profile(zen_hip_nmf_t h, int enable) { return profile(h, enable); }
 
 int zen_hip_nmf_profile_get(zen_hip_nmf_t h, double ms[ZEN_HIP_NMF_KERNELS], unsigned long long bytes[ZEN_HIP_NMF_KERNELS],
                             unsigned long long launches[ZEN_HIP_NMF_KERNELS])
 {
-	if (!h || !ms || !bytes || !launches)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "nmf_profile_get: null argument");
-	return h->prof.drain(ms, bytes, launches);
+	return profile_get(h, ms, bytes, launches, "nmf");
 }
 
 int zen_hip_nmf_init(unsigned long long seed, size_t count, float* out)

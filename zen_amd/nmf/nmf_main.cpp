@@ -21,19 +21,16 @@
 #include <string>
 #include <vector>
 
+#include "demo.h"
 #include "wav.h"
 #include "zen_hip.h"
 #include "zen_hip_nmf.h"
 
+using zen::demo::option;
+
 namespace {
 
-void check(int rc, const char* what, const char* msg)
-{
-	if (rc != ZEN_HIP_OK)
-		throw std::runtime_error(std::string(what) + ": " + msg);
-}
-#define ZEN(call) check((call), #call, zen_hip_last_error())
-#define NMF(call) check((call), #call, zen_hip_nmf_last_error())
+#define NMF(call) ZEN_LIB(zen_hip_nmf_last_error, call)
 
 int usage()
 {
@@ -133,33 +130,6 @@ Dictionary load(const std::string& path)
 	return d;
 }
 
-void peak_normalise(std::vector<float>& x) // as `zen offline`; a stem of zeros is left as it is
-{
-	auto limits = std::minmax_element(x.begin(), x.end());
-	const float real_max = std::max(-1 * (*limits.first), *limits.second);
-	if (!(real_max > 0.0f))
-		return;
-	for (float& v : x)
-		v /= real_max;
-}
-
-std::vector<float> mono_of(const std::string& infile, int* rate)
-{
-	zen::wav::AudioData fd;
-	zen::wav::load(fd, infile);
-	std::vector<float> mono;
-	if (fd.channelCount == 2) {
-		mono.resize(fd.samples.size() / 2);
-		zen::wav::stereo_to_mono(fd.samples.data(), mono.data(), fd.samples.size());
-	} else {
-		mono = fd.samples;
-	}
-	if (mono.empty())
-		throw std::runtime_error("no samples in " + infile);
-	*rate = (int)fd.sampleRate;
-	return mono;
-}
-
 } // namespace
 
 int main(int argc, char** argv)
@@ -173,26 +143,21 @@ int main(int argc, char** argv)
 	unsigned long long seed = 0;
 	long iterations = 100;
 	for (int i = 2; i < argc; ++i) {
-		char* end = nullptr;
 		if (!strcmp(argv[i], "-o") && i + 1 < argc) {
 			outname = argv[++i];
 		} else if (!strcmp(argv[i], "-d") && i + 1 < argc && !train) {
 			dict_files.push_back(argv[++i]);
 		} else if (!strcmp(argv[i], "--nfft") && i + 1 < argc && train) {
-			nfft = (size_t)strtoull(argv[++i], &end, 10);
-			if (*end)
+			if (!option(argv[++i], &nfft))
 				return usage();
 		} else if (!strcmp(argv[i], train ? "--components" : "--free") && i + 1 < argc) {
-			components = (size_t)strtoull(argv[++i], &end, 10);
-			if (*end)
+			if (!option(argv[++i], &components))
 				return usage();
 		} else if (!strcmp(argv[i], "--iterations") && i + 1 < argc) {
-			iterations = strtol(argv[++i], &end, 10);
-			if (*end || iterations < 0 || iterations > 1000000)
+			if (!option(argv[++i], &iterations) || iterations < 0 || iterations > 1000000)
 				return usage();
 		} else if (!strcmp(argv[i], "--seed") && i + 1 < argc) {
-			seed = strtoull(argv[++i], &end, 10);
-			if (*end)
+			if (!option(argv[++i], &seed))
 				return usage();
 		} else if (argv[i][0] == '-' || !infile.empty()) {
 			return usage();
@@ -204,10 +169,11 @@ int main(int argc, char** argv)
 		return usage();
 	zen_hip_nmf_t nm = nullptr;
 	float* dev = nullptr;
-	int status = 0;
-	try {
+	const auto body = [&] {
 		int rate = 0;
-		const std::vector<float> mono = mono_of(infile, &rate);
+		const std::vector<float> mono = zen::demo::load_mono(infile, &rate);
+		if (mono.empty())
+			throw std::runtime_error("no samples in " + infile);
 		const size_t n = mono.size();
 		std::vector<Dictionary> dicts;
 		size_t fixed = 0;
@@ -259,23 +225,14 @@ int main(int argc, char** argv)
 			for (size_t g = 0; g < G; ++g) {
 				std::vector<float> stem(n);
 				ZEN(zen_hip_memcpy_d2h(stem.data(), dev + o_s + g * up4(n), sizeof(float) * n));
-				peak_normalise(stem);
+				zen::demo::peak_normalise(stem);
 				zen::wav::encode_pcm16_mono(stem, rate, outname + "_" + std::to_string(g) + ".wav");
 			}
 			printf("frames: %zu, %zu spectra held and %zu learned, %zu stems after %ld iterations\n", m, fixed, components, G, iterations);
 		}
-	} catch (const std::exception& e) {
-		fprintf(stderr, "zen-nmf: %s\n", e.what());
-		status = 1;
-	}
-	zen_hip_nmf_destroy(nm);
-	zen_hip_free(dev);
-	if (status == 0) { // as `zen`: a red zone found overwritten is an error of its own
-		zen_hip_memcheck_report rep;
-		if (zen_hip_memcheck(&rep) == ZEN_HIP_OK && rep.corrupt_words) {
-			fprintf(stderr, "zen-nmf: memory check: %s\n", rep.first_message);
-			status = 86;
-		}
-	}
-	return status;
+	};
+	return zen::demo::run("zen-nmf", body, [&] {
+		zen_hip_nmf_destroy(nm);
+		zen_hip_free(dev);
+	});
 }

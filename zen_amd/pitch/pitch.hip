@@ -27,11 +27,10 @@ enum { K_PAD = 0, K_FWD = 1, K_POWER = 2, K_INV = 3, K_PICK = 4, K_COUNT = ZEN_H
 
 } // namespace
 
-struct zen_hip_pitch {
+struct zen_hip_pitch : Handle<K_COUNT> {
 	float fs = 0.f;
 	size_t n = 0, S = 0, max_chunks = 0;
 	zen_hip_fft_t fft = nullptr; // 2n points
-	hipStream_t stream = nullptr;
 	float* z = nullptr;        // S * max_chunks rows of 2n complex values
 	double* prefix = nullptr;  // S * max_chunks rows of n + 1 doubles
 	float* stage_in = nullptr; // the host calls' device rows: S rows of max_chunks * n samples
@@ -39,17 +38,9 @@ struct zen_hip_pitch {
 	float* stage_nsdf = nullptr;                       // S rows of max_chunks * n
 	size_t stage_in_row = 0;
 	unsigned long long chunks = 0;
-	DeviceTally mem;
-	Profiler<K_COUNT> prof;
 };
 
 namespace {
-
-template <class T>
-int alloc(zen_hip_pitch* h, T** p, size_t count)
-{
-	return counted_malloc(&h->mem, (void**)p, sizeof(T) * count, "zen_hip_malloc((void**)p, sizeof(T) * count)");
-}
 
 // `cs` chunks of every stream from chunk c0 of the call on
 int run_slice(zen_hip_pitch* h, const float* in_dev, size_t in_stride, size_t step, size_t c0, size_t cs, float* pitch, float* period,
@@ -111,15 +102,11 @@ int check_rows(const char* who, zen_hip_pitch_t h, const void* in, size_t n_chun
 	return ZEN_HIP_OK;
 }
 
-// rows of `cnt` floats between host and device memory
+// rows of `cnt` floats between host and device memory, one per stream
 int copy_rows(zen_hip_pitch* h, void* dst, size_t dst_stride, const void* src, size_t src_stride, size_t cnt, hipMemcpyKind kind)
 {
-	if (cnt)
-		ZA_HIP(hipMemcpy2DAsync(dst, sizeof(float) * dst_stride, src, sizeof(float) * src_stride, sizeof(float) * cnt, h->S, kind, h->stream));
-	return ZEN_HIP_OK;
+	return h->copy_rows(dst, dst_stride, src, src_stride, cnt, h->S, kind);
 }
-
-bool is_pow2(size_t x) { return x && (x & (x - 1)) == 0; }
 
 } // namespace
 
@@ -149,13 +136,13 @@ int zen_hip_pitch_create(float fs, size_t n, size_t n_streams, size_t max_chunks
 		const size_t rows = n_streams * max_chunks;
 		ZA_ZEN(zen_hip_fft_create(2 * n, &h->fft));
 		ZA_HIP(zen_pitch::prepare_pick((int)n));
-		ZA_TRY(alloc(h, &h->z, rows * 4 * n));
-		ZA_TRY(alloc(h, &h->prefix, rows * (n + 1)));
+		ZA_TRY(h->alloc(&h->z, rows * 4 * n));
+		ZA_TRY(h->alloc(&h->prefix, rows * (n + 1)));
 		h->stage_in_row = max_chunks * n;
-		ZA_TRY(alloc(h, &h->stage_in, n_streams * h->stage_in_row));
+		ZA_TRY(h->alloc(&h->stage_in, n_streams * h->stage_in_row));
 		for (float*& p : h->stage_out)
-			ZA_TRY(alloc(h, &p, rows));
-		ZA_TRY(alloc(h, &h->stage_nsdf, rows * n));
+			ZA_TRY(h->alloc(&p, rows));
+		ZA_TRY(h->alloc(&h->stage_nsdf, rows * n));
 		// whatever the transform allocates for its largest batch, up front: one run on zeros
 		ZA_HIP(hipMemsetAsync(h->z, 0, sizeof(float) * rows * 4 * n, h->stream));
 		ZA_ZEN(zen_hip_fft_exec_batched(h->fft, h->z, rows, 0, h->stream));
@@ -173,22 +160,12 @@ int zen_hip_pitch_destroy(zen_hip_pitch_t h)
 		return ZEN_HIP_OK;
 	(void)hipStreamSynchronize(h->stream);
 	zen_hip_fft_destroy(h->fft);
-	void* bufs[] = {h->z, h->prefix, h->stage_in, h->stage_out[0], h->stage_out[1], h->stage_out[2], h->stage_nsdf};
-	for (void* b : bufs)
-		(void)zen_hip_free(b);
-	h->prof.release();
+	h->release({h->z, h->prefix, h->stage_in, h->stage_out[0], h->stage_out[1], h->stage_out[2], h->stage_nsdf});
 	delete h;
 	return ZEN_HIP_OK;
 }
 
-int zen_hip_pitch_set_stream(zen_hip_pitch_t h, void* stream)
-{
-	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pitch_set_stream: null handle");
-	ZA_HIP(hipStreamSynchronize(h->stream));
-	h->stream = (hipStream_t)stream;
-	return ZEN_HIP_OK;
-}
+int zen_hip_pitch_set_stream(zen_hip_pitch_t h, void* stream) { return set_stream(h, stream, "pitch"); }
 
 int zen_hip_pitch_run_device(zen_hip_pitch_t h, const float* in_dev, size_t in_stride, size_t n_chunks, size_t step, float* pitch_dev,
                              float* period_dev, float* clarity_dev, float* nsdf_dev, size_t out_stride)
@@ -246,20 +223,12 @@ int zen_hip_pitch_stats(zen_hip_pitch_t h, zen_hip_pitch_stats_t* out)
 	return ZEN_HIP_OK;
 }
 
-int zen_hip_pitch_profile(zen_hip_pitch_t h, int enable)
-{
-	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
-	h->prof.on = enable != 0;
-	return ZEN_HIP_OK;
-}
+int zen_hip_pitch_profile(zen_hip_pitch_t h, int enable) { return profile(h, enable); }
 
 int zen_hip_pitch_profile_get(zen_hip_pitch_t h, double ms[ZEN_HIP_PITCH_KERNELS], unsigned long long bytes[ZEN_HIP_PITCH_KERNELS],
                               unsigned long long launches[ZEN_HIP_PITCH_KERNELS])
 {
-	if (!h || !ms || !bytes || !launches)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pitch_profile_get: null argument");
-	return h->prof.drain(ms, bytes, launches);
+	return profile_get(h, ms, bytes, launches, "pitch");
 }
 
 } // extern "C"

@@ -14,19 +14,16 @@
 #include <string>
 #include <vector>
 
+#include "demo.h"
 #include "wav.h"
 #include "zen_hip.h"
 #include "zen_hip_pitch.h"
 
+using zen::demo::option;
+
 namespace {
 
-void check(int rc, const char* what, const char* msg)
-{
-	if (rc != ZEN_HIP_OK)
-		throw std::runtime_error(std::string(what) + ": " + msg);
-}
-#define ZEN(call) check((call), #call, zen_hip_last_error())
-#define PITCH(call) check((call), #call, zen_hip_pitch_last_error())
+#define PITCH(call) ZEN_LIB(zen_hip_pitch_last_error, call)
 
 int usage()
 {
@@ -42,14 +39,11 @@ int main(int argc, char** argv)
 	size_t chunk = 4096;
 	float beta = 2.5f;
 	for (int i = 1; i < argc; ++i) {
-		char* end = nullptr;
 		if (!strcmp(argv[i], "--chunk") && i + 1 < argc) {
-			chunk = (size_t)strtoull(argv[++i], &end, 10);
-			if (*end)
+			if (!option(argv[++i], &chunk))
 				return usage();
 		} else if (!strcmp(argv[i], "--beta") && i + 1 < argc) {
-			beta = strtof(argv[++i], &end);
-			if (*end)
+			if (!option(argv[++i], &beta))
 				return usage();
 		} else if (argv[i][0] == '-' || !infile.empty()) {
 			return usage();
@@ -62,19 +56,11 @@ int main(int argc, char** argv)
 	zen_hip_hpr_t hpr = nullptr;
 	zen_hip_pitch_t pt = nullptr;
 	float *dev = nullptr, *out = nullptr;
-	int status = 0;
-	try {
-		zen::wav::AudioData fd;
-		zen::wav::load(fd, infile);
-		std::vector<float> mono;
-		if (fd.channelCount == 2) {
-			mono.resize(fd.samples.size() / 2);
-			zen::wav::stereo_to_mono(fd.samples.data(), mono.data(), fd.samples.size());
-		} else {
-			mono = fd.samples;
-		}
+	const auto body = [&] {
+		int rate = 0;
+		const std::vector<float> mono = zen::demo::load_mono(infile, &rate);
 		const size_t n_chunks = mono.size() / chunk, len = n_chunks * chunk;
-		const float fs = (float)fd.sampleRate;
+		const float fs = (float)rate;
 		ZEN(zen_hip_init(0));
 		PITCH(zen_hip_pitch_create(fs, chunk, 2, 0, &pt)); // stream 0: the recording, stream 1: its harmonic part
 		ZEN(zen_hip_hpr_create(fs, chunk, beta, ZEN_HIP_OUTPUT_HARMONIC, ZEN_HIP_TIME_CAUSAL, 1, 1, 0, &hpr));
@@ -90,20 +76,11 @@ int main(int argc, char** argv)
 				printf("t: %.3f,\tpitch (+HPR): %.2f,\tpitch (-HPR): %.2f\n", (double)(c * chunk) / (double)fs, (double)pitch[n_chunks + c],
 				       (double)pitch[c]);
 		}
-	} catch (const std::exception& e) {
-		fprintf(stderr, "pitch-track: %s\n", e.what());
-		status = 1;
-	}
-	zen_hip_pitch_destroy(pt);
-	zen_hip_hpr_destroy(hpr);
-	zen_hip_free(dev);
-	zen_hip_free(out);
-	if (status == 0) { // as `zen`: a red zone found overwritten is an error of its own
-		zen_hip_memcheck_report rep;
-		if (zen_hip_memcheck(&rep) == ZEN_HIP_OK && rep.corrupt_words) {
-			fprintf(stderr, "pitch-track: memory check: %s\n", rep.first_message);
-			status = 86;
-		}
-	}
-	return status;
+	};
+	return zen::demo::run("pitch-track", body, [&] {
+		zen_hip_pitch_destroy(pt);
+		zen_hip_hpr_destroy(hpr);
+		zen_hip_free(dev);
+		zen_hip_free(out);
+	});
 }

@@ -321,9 +321,7 @@ int zen_hip_ragged_profile(zen_hip_ragged_t h, int enable)
 
 int zen_hip_ragged_profile_get(zen_hip_ragged_t h, double ms[3], unsigned long long bytes[3], unsigned long long launches[3])
 {
-	if (!h || !ms || !bytes || !launches)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "ragged_profile_get: null argument");
-	return h->prof.drain(ms, bytes, launches);
+	return profile_get(h, ms, bytes, launches, "ragged");
 }
 
 int zen_hip_ragged_profile_get_engine(zen_hip_ragged_t h, int pass, double ms[6], unsigned long long launches[6])

@@ -40,13 +40,12 @@ size_t lag_points(size_t m)
 
 } // namespace
 
-struct zen_hip_repet {
+struct zen_hip_repet : Handle<K_COUNT> {
 	float fs = 0.f;
 	size_t N = 0, H = 0, bins = 0, v_stride = 0, C = 0, max_samples = 0, max_frames = 0, max_lag = 0;
 	double tmin = 0.8, tmax = 8.0, highpass = 100.0;
 	zen_hip_fft_t fft = nullptr;          // N points
 	std::vector<zen_hip_fft_t> lag_fft;   // 64, 128, .., max_lag points
-	hipStream_t stream = nullptr;
 	float* rows = nullptr;      // C * max_frames rows of N complex values
 	float* v = nullptr;         // C * max_frames rows of v_stride floats
 	float* s = nullptr;         // max_frames rows of v_stride floats: the repeating segment of the clip at hand
@@ -58,17 +57,9 @@ struct zen_hip_repet {
 	std::vector<float> braw_host;   // C rows of max_frames floats
 	std::vector<size_t> period;     // C
 	unsigned long long calls = 0, clips = 0, searches = 0;
-	DeviceTally mem;
-	Profiler<K_COUNT> prof;
 };
 
 namespace {
-
-template <class T>
-int alloc(zen_hip_repet* h, T** p, size_t count)
-{
-	return counted_malloc(&h->mem, (void**)p, sizeof(T) * count, "zen_hip_malloc((void**)p, sizeof(T) * count)");
-}
 
 zen_hip_fft_t lag_handle(const zen_hip_repet* h, size_t L)
 {
@@ -257,8 +248,7 @@ int separate(const char* who, zen_hip_repet* h, const float* in, size_t in_strid
 // rows of `cnt` floats between host and device memory
 int copy_rows(zen_hip_repet* h, void* dst, size_t dst_stride, const void* src, size_t src_stride, size_t cnt, hipMemcpyKind kind)
 {
-	ZA_HIP(hipMemcpy2DAsync(dst, sizeof(float) * dst_stride, src, sizeof(float) * src_stride, sizeof(float) * cnt, h->C, kind, h->stream));
-	return ZEN_HIP_OK;
+	return h->copy_rows(dst, dst_stride, src, src_stride, cnt, h->C, kind);
 }
 
 } // namespace
@@ -303,15 +293,15 @@ int zen_hip_repet_create(float fs, size_t nfft, size_t n_clips, size_t max_sampl
 			ZA_ZEN(zen_hip_fft_create(L, &f));
 			h->lag_fft.push_back(f);
 		}
-		ZA_TRY(alloc(h, &h->rows, frames * 2 * nfft));
-		ZA_TRY(alloc(h, &h->v, frames * h->v_stride));
-		ZA_TRY(alloc(h, &h->s, h->max_frames * h->v_stride));
-		ZA_TRY(alloc(h, &h->lag, h->bins * 2 * h->max_lag));
-		ZA_TRY(alloc(h, &h->braw, frames));
-		ZA_TRY(alloc(h, &h->tables, tab.size()));
-		ZA_TRY(alloc(h, &h->stage_in, n_clips * max_samples));
+		ZA_TRY(h->alloc(&h->rows, frames * 2 * nfft));
+		ZA_TRY(h->alloc(&h->v, frames * h->v_stride));
+		ZA_TRY(h->alloc(&h->s, h->max_frames * h->v_stride));
+		ZA_TRY(h->alloc(&h->lag, h->bins * 2 * h->max_lag));
+		ZA_TRY(h->alloc(&h->braw, frames));
+		ZA_TRY(h->alloc(&h->tables, tab.size()));
+		ZA_TRY(h->alloc(&h->stage_in, n_clips * max_samples));
 		for (float*& p : h->stage_out)
-			ZA_TRY(alloc(h, &p, n_clips * max_samples));
+			ZA_TRY(h->alloc(&p, n_clips * max_samples));
 		ZA_ZEN(zen_hip_memcpy_h2d(h->tables, tab.data(), sizeof(float) * tab.size()));
 		// whatever the transforms allocate for their largest batches, up front: one run each on zeros
 		ZA_HIP(hipMemsetAsync(h->rows, 0, sizeof(float) * frames * 2 * nfft, h->stream));
@@ -335,22 +325,12 @@ int zen_hip_repet_destroy(zen_hip_repet_t h)
 	zen_hip_fft_destroy(h->fft);
 	for (zen_hip_fft_t f : h->lag_fft)
 		zen_hip_fft_destroy(f);
-	void* bufs[] = {h->rows, h->v, h->s, h->lag, h->braw, h->tables, h->stage_in, h->stage_out[0], h->stage_out[1]};
-	for (void* b : bufs)
-		(void)zen_hip_free(b);
-	h->prof.release();
+	h->release({h->rows, h->v, h->s, h->lag, h->braw, h->tables, h->stage_in, h->stage_out[0], h->stage_out[1]});
 	delete h;
 	return ZEN_HIP_OK;
 }
 
-int zen_hip_repet_set_stream(zen_hip_repet_t h, void* stream)
-{
-	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "repet_set_stream: null handle");
-	ZA_HIP(hipStreamSynchronize(h->stream));
-	h->stream = (hipStream_t)stream;
-	return ZEN_HIP_OK;
-}
+int zen_hip_repet_set_stream(zen_hip_repet_t h, void* stream) { return set_stream(h, stream, "repet"); }
 
 int zen_hip_repet_set_params(zen_hip_repet_t h, double tmin_s, double tmax_s, double highpass_hz)
 {
@@ -440,20 +420,12 @@ int zen_hip_repet_stats(zen_hip_repet_t h, zen_hip_repet_stats_t* out)
 	return ZEN_HIP_OK;
 }
 
-int zen_hip_repet_profile(zen_hip_repet_t h, int enable)
-{
-	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
-	h->prof.on = enable != 0;
-	return ZEN_HIP_OK;
-}
+int zen_hip_repet_profile(zen_hip_repet_t h, int enable) { return profile(h, enable); }
 
 int zen_hip_repet_profile_get(zen_hip_repet_t h, double ms[ZEN_HIP_REPET_KERNELS], unsigned long long bytes[ZEN_HIP_REPET_KERNELS],
                               unsigned long long launches[ZEN_HIP_REPET_KERNELS])
 {
-	if (!h || !ms || !bytes || !launches)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "repet_profile_get: null argument");
-	return h->prof.drain(ms, bytes, launches);
+	return profile_get(h, ms, bytes, launches, "repet");
 }
 
 int zen_hip_repet_find_period(const float* braw, size_t m, size_t jmin, size_t jmax, size_t* period, double* score)

@@ -14,19 +14,16 @@
 #include <string>
 #include <vector>
 
+#include "demo.h"
 #include "wav.h"
 #include "zen_hip.h"
 #include "zen_hip_repet.h"
 
+using zen::demo::option;
+
 namespace {
 
-void check(int rc, const char* what, const char* msg)
-{
-	if (rc != ZEN_HIP_OK)
-		throw std::runtime_error(std::string(what) + ": " + msg);
-}
-#define ZEN(call) check((call), #call, zen_hip_last_error())
-#define REPET(call) check((call), #call, zen_hip_repet_last_error())
+#define REPET(call) ZEN_LIB(zen_hip_repet_last_error, call)
 
 int usage()
 {
@@ -44,20 +41,16 @@ int main(int argc, char** argv)
 	size_t nfft = 2048;
 	double period_s = 0.0, highpass = 100.0;
 	for (int i = 1; i < argc; ++i) {
-		char* end = nullptr;
 		if (!strcmp(argv[i], "-o") && i + 1 < argc) {
 			prefix = argv[++i];
 		} else if (!strcmp(argv[i], "--nfft") && i + 1 < argc) {
-			nfft = (size_t)strtoull(argv[++i], &end, 10);
-			if (*end)
+			if (!option(argv[++i], &nfft))
 				return usage();
 		} else if (!strcmp(argv[i], "--period") && i + 1 < argc) {
-			period_s = strtod(argv[++i], &end);
-			if (*end || !(period_s > 0.0))
+			if (!option(argv[++i], &period_s) || !(period_s > 0.0))
 				return usage();
 		} else if (!strcmp(argv[i], "--highpass") && i + 1 < argc) {
-			highpass = strtod(argv[++i], &end);
-			if (*end || !(highpass >= 0.0))
+			if (!option(argv[++i], &highpass) || !(highpass >= 0.0))
 				return usage();
 		} else if (argv[i][0] == '-' || !infile.empty()) {
 			return usage();
@@ -69,21 +62,13 @@ int main(int argc, char** argv)
 		return usage();
 	zen_hip_repet_t rp = nullptr;
 	float* dev = nullptr;
-	int status = 0;
-	try {
-		zen::wav::AudioData fd;
-		zen::wav::load(fd, infile);
-		std::vector<float> mono;
-		if (fd.channelCount == 2) {
-			mono.resize(fd.samples.size() / 2);
-			zen::wav::stereo_to_mono(fd.samples.data(), mono.data(), fd.samples.size());
-		} else {
-			mono = fd.samples;
-		}
+	const auto body = [&] {
+		int rate = 0;
+		const std::vector<float> mono = zen::demo::load_mono(infile, &rate);
 		const size_t n = mono.size(), hop = nfft / 2;
 		if (n == 0)
 			throw std::runtime_error("no samples in " + infile);
-		const float fs = (float)fd.sampleRate;
+		const float fs = (float)rate;
 		ZEN(zen_hip_init(0));
 		REPET(zen_hip_repet_create(fs, nfft, 1, n, &rp));
 		REPET(zen_hip_repet_set_params(rp, 0.8, 8.0, highpass));
@@ -99,24 +84,15 @@ int main(int argc, char** argv)
 		REPET(zen_hip_repet_separate_device(rp, dev, n, n, &given, dev + n, dev + 2 * n, n, &used, nullptr, 0));
 		ZEN(zen_hip_memcpy_d2h(bg.data(), dev + n, sizeof(float) * n));
 		ZEN(zen_hip_memcpy_d2h(fg.data(), dev + 2 * n, sizeof(float) * n));
-		zen::wav::encode_pcm16_mono(bg, fd.sampleRate, prefix + "_background.wav");
-		zen::wav::encode_pcm16_mono(fg, fd.sampleRate, prefix + "_foreground.wav");
+		zen::wav::encode_pcm16_mono(bg, rate, prefix + "_background.wav");
+		zen::wav::encode_pcm16_mono(fg, rate, prefix + "_foreground.wav");
 		if (used)
 			printf("period: %zu frames, %.4f s\n", used, (double)(used * hop) / (double)fs);
 		else
 			printf("period: none found\n");
-	} catch (const std::exception& e) {
-		fprintf(stderr, "zen-repet: %s\n", e.what());
-		status = 1;
-	}
-	zen_hip_repet_destroy(rp);
-	zen_hip_free(dev);
-	if (status == 0) { // as `zen`: a red zone found overwritten is an error of its own
-		zen_hip_memcheck_report rep;
-		if (zen_hip_memcheck(&rep) == ZEN_HIP_OK && rep.corrupt_words) {
-			fprintf(stderr, "zen-repet: memory check: %s\n", rep.first_message);
-			status = 86;
-		}
-	}
-	return status;
+	};
+	return zen::demo::run("zen-repet", body, [&] {
+		zen_hip_repet_destroy(rp);
+		zen_hip_free(dev);
+	});
 }

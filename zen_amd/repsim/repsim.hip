@@ -37,14 +37,13 @@ size_t round_up(size_t v, size_t q) { return (v + q - 1) / q * q; }
 
 } // namespace
 
-struct zen_hip_repsim {
+struct zen_hip_repsim : Handle<K_COUNT> {
 	float fs = 0.f;
 	size_t N = 0, H = 0, bins = 0, v_stride = 0, C = 0, max_samples = 0, max_frames = 0, band = 0, s_stride = 0;
 	double threshold = 0.0, distance = 1.0, highpass = 100.0;
 	size_t number = 100;
 	bool mfma = DEFAULT_MFMA;
 	zen_hip_fft_t fft = nullptr; // N points
-	hipStream_t stream = nullptr;
 	float* rows = nullptr;      // C * max_frames rows of N complex values
 	float* v = nullptr;         // C * max_frames rows of v_stride floats
 	float* u = nullptr;         // max_frames rows of v_stride floats: the repeating spectrogram of the clip at hand
@@ -55,17 +54,9 @@ struct zen_hip_repsim {
 	float* stage_in = nullptr;  // the host calls' device rows: C rows of max_samples samples
 	float* stage_out[2] = {nullptr, nullptr};
 	unsigned long long calls = 0, clips = 0, bands = 0;
-	DeviceTally mem;
-	Profiler<K_COUNT> prof;
 };
 
 namespace {
-
-template <class T>
-int alloc(zen_hip_repsim* h, T** p, size_t count)
-{
-	return counted_malloc(&h->mem, (void**)p, sizeof(T) * count, "zen_hip_malloc((void**)p, sizeof(T) * count)");
-}
 
 // steps 1-2 for every clip
 int spectra(zen_hip_repsim* h, const float* in, size_t in_stride, size_t n, size_t m)
@@ -196,8 +187,7 @@ int copy_selection(zen_hip_repsim* h, size_t n, int* counts, int* indices, hipMe
 // rows of `cnt` floats between host and device memory
 int copy_rows(zen_hip_repsim* h, void* dst, size_t dst_stride, const void* src, size_t src_stride, size_t cnt, hipMemcpyKind kind)
 {
-	ZA_HIP(hipMemcpy2DAsync(dst, sizeof(float) * dst_stride, src, sizeof(float) * src_stride, sizeof(float) * cnt, h->C, kind, h->stream));
-	return ZEN_HIP_OK;
+	return h->copy_rows(dst, dst_stride, src, src_stride, cnt, h->C, kind);
 }
 
 int check_matrix(const char* who, const void* p, const void* q, size_t m)
@@ -258,16 +248,16 @@ int zen_hip_repsim_create(float fs, size_t nfft, size_t n_clips, size_t max_samp
 		const size_t frames = n_clips * h->max_frames;
 		const std::vector<float> tab = stft_tables(nfft);
 		ZA_ZEN(zen_hip_fft_create(nfft, &h->fft));
-		ZA_TRY(alloc(h, &h->rows, frames * 2 * nfft));
-		ZA_TRY(alloc(h, &h->v, frames * h->v_stride));
-		ZA_TRY(alloc(h, &h->u, h->max_frames * h->v_stride));
-		ZA_TRY(alloc(h, &h->sband, h->band * h->s_stride));
-		ZA_TRY(alloc(h, &h->idx, frames * KMAX));
-		ZA_TRY(alloc(h, &h->counts, frames));
-		ZA_TRY(alloc(h, &h->tables, tab.size()));
-		ZA_TRY(alloc(h, &h->stage_in, n_clips * max_samples));
+		ZA_TRY(h->alloc(&h->rows, frames * 2 * nfft));
+		ZA_TRY(h->alloc(&h->v, frames * h->v_stride));
+		ZA_TRY(h->alloc(&h->u, h->max_frames * h->v_stride));
+		ZA_TRY(h->alloc(&h->sband, h->band * h->s_stride));
+		ZA_TRY(h->alloc(&h->idx, frames * KMAX));
+		ZA_TRY(h->alloc(&h->counts, frames));
+		ZA_TRY(h->alloc(&h->tables, tab.size()));
+		ZA_TRY(h->alloc(&h->stage_in, n_clips * max_samples));
 		for (float*& p : h->stage_out)
-			ZA_TRY(alloc(h, &p, n_clips * max_samples));
+			ZA_TRY(h->alloc(&p, n_clips * max_samples));
 		ZA_ZEN(zen_hip_memcpy_h2d(h->tables, tab.data(), sizeof(float) * tab.size()));
 		// whatever the transform allocates for its largest batch, up front: one run on zeros
 		ZA_HIP(hipMemsetAsync(h->rows, 0, sizeof(float) * frames * 2 * nfft, h->stream));
@@ -286,22 +276,12 @@ int zen_hip_repsim_destroy(zen_hip_repsim_t h)
 		return ZEN_HIP_OK;
 	(void)hipStreamSynchronize(h->stream);
 	zen_hip_fft_destroy(h->fft);
-	void* bufs[] = {h->rows, h->v, h->u, h->sband, h->idx, h->counts, h->tables, h->stage_in, h->stage_out[0], h->stage_out[1]};
-	for (void* b : bufs)
-		(void)zen_hip_free(b);
-	h->prof.release();
+	h->release({h->rows, h->v, h->u, h->sband, h->idx, h->counts, h->tables, h->stage_in, h->stage_out[0], h->stage_out[1]});
 	delete h;
 	return ZEN_HIP_OK;
 }
 
-int zen_hip_repsim_set_stream(zen_hip_repsim_t h, void* stream)
-{
-	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "repsim_set_stream: null handle");
-	ZA_HIP(hipStreamSynchronize(h->stream));
-	h->stream = (hipStream_t)stream;
-	return ZEN_HIP_OK;
-}
+int zen_hip_repsim_set_stream(zen_hip_repsim_t h, void* stream) { return set_stream(h, stream, "repsim"); }
 
 int zen_hip_repsim_set_params(zen_hip_repsim_t h, double threshold, double distance_s, size_t number, double highpass_hz)
 {
@@ -405,20 +385,12 @@ int zen_hip_repsim_stats(zen_hip_repsim_t h, zen_hip_repsim_stats_t* out)
 	return ZEN_HIP_OK;
 }
 
-int zen_hip_repsim_profile(zen_hip_repsim_t h, int enable)
-{
-	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
-	h->prof.on = enable != 0;
-	return ZEN_HIP_OK;
-}
+int zen_hip_repsim_profile(zen_hip_repsim_t h, int enable) { return profile(h, enable); }
 
 int zen_hip_repsim_profile_get(zen_hip_repsim_t h, double ms[ZEN_HIP_REPSIM_KERNELS], unsigned long long bytes[ZEN_HIP_REPSIM_KERNELS],
                                unsigned long long launches[ZEN_HIP_REPSIM_KERNELS])
 {
-	if (!h || !ms || !bytes || !launches)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "repsim_profile_get: null argument");
-	return h->prof.drain(ms, bytes, launches);
+	return profile_get(h, ms, bytes, launches, "repsim");
 }
 
 int zen_hip_repsim_table(size_t nfft, int which, float* out, size_t cap)

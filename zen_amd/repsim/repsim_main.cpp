@@ -15,19 +15,16 @@
 #include <string>
 #include <vector>
 
+#include "demo.h"
 #include "wav.h"
 #include "zen_hip.h"
 #include "zen_hip_repsim.h"
 
+using zen::demo::option;
+
 namespace {
 
-void check(int rc, const char* what, const char* msg)
-{
-	if (rc != ZEN_HIP_OK)
-		throw std::runtime_error(std::string(what) + ": " + msg);
-}
-#define ZEN(call) check((call), #call, zen_hip_last_error())
-#define REPSIM(call) check((call), #call, zen_hip_repsim_last_error())
+#define REPSIM(call) ZEN_LIB(zen_hip_repsim_last_error, call)
 
 int usage()
 {
@@ -47,28 +44,22 @@ int main(int argc, char** argv)
 	size_t nfft = 2048, number = 100;
 	double distance = 1.0, threshold = 0.0, highpass = 100.0;
 	for (int i = 1; i < argc; ++i) {
-		char* end = nullptr;
 		if (!strcmp(argv[i], "-o") && i + 1 < argc) {
 			prefix = argv[++i];
 		} else if (!strcmp(argv[i], "--nfft") && i + 1 < argc) {
-			nfft = (size_t)strtoull(argv[++i], &end, 10);
-			if (*end)
+			if (!option(argv[++i], &nfft))
 				return usage();
 		} else if (!strcmp(argv[i], "--number") && i + 1 < argc) {
-			number = (size_t)strtoull(argv[++i], &end, 10);
-			if (*end)
+			if (!option(argv[++i], &number))
 				return usage();
 		} else if (!strcmp(argv[i], "--distance") && i + 1 < argc) {
-			distance = strtod(argv[++i], &end);
-			if (*end || !(distance >= 0.0))
+			if (!option(argv[++i], &distance) || !(distance >= 0.0))
 				return usage();
 		} else if (!strcmp(argv[i], "--threshold") && i + 1 < argc) {
-			threshold = strtod(argv[++i], &end);
-			if (*end || !(threshold >= 0.0))
+			if (!option(argv[++i], &threshold) || !(threshold >= 0.0))
 				return usage();
 		} else if (!strcmp(argv[i], "--highpass") && i + 1 < argc) {
-			highpass = strtod(argv[++i], &end);
-			if (*end || !(highpass >= 0.0))
+			if (!option(argv[++i], &highpass) || !(highpass >= 0.0))
 				return usage();
 		} else if (argv[i][0] == '-' || !infile.empty()) {
 			return usage();
@@ -81,21 +72,13 @@ int main(int argc, char** argv)
 	zen_hip_repsim_t rs = nullptr;
 	float* dev = nullptr;
 	int* counts_dev = nullptr;
-	int status = 0;
-	try {
-		zen::wav::AudioData fd;
-		zen::wav::load(fd, infile);
-		std::vector<float> mono;
-		if (fd.channelCount == 2) {
-			mono.resize(fd.samples.size() / 2);
-			zen::wav::stereo_to_mono(fd.samples.data(), mono.data(), fd.samples.size());
-		} else {
-			mono = fd.samples;
-		}
+	const auto body = [&] {
+		int rate = 0;
+		std::vector<float> mono = zen::demo::load_mono(infile, &rate);
 		const size_t n = mono.size(), hop = nfft / 2;
 		if (n == 0)
 			throw std::runtime_error("no samples in " + infile);
-		const float fs = (float)fd.sampleRate;
+		const float fs = (float)rate;
 		ZEN(zen_hip_init(0));
 		REPSIM(zen_hip_repsim_create(fs, nfft, 1, n, &rs));
 		REPSIM(zen_hip_repsim_set_params(rs, threshold, distance, number, highpass));
@@ -109,25 +92,16 @@ int main(int argc, char** argv)
 		ZEN(zen_hip_memcpy_d2h(bg.data(), dev + n, sizeof(float) * n));
 		ZEN(zen_hip_memcpy_d2h(fg.data(), dev + 2 * n, sizeof(float) * n));
 		ZEN(zen_hip_memcpy_d2h(counts.data(), counts_dev, sizeof(int) * m));
-		zen::wav::encode_pcm16_mono(bg, fd.sampleRate, prefix + "_background.wav");
-		zen::wav::encode_pcm16_mono(fg, fd.sampleRate, prefix + "_foreground.wav");
+		zen::wav::encode_pcm16_mono(bg, rate, prefix + "_background.wav");
+		zen::wav::encode_pcm16_mono(fg, rate, prefix + "_foreground.wav");
 		unsigned long long total = 0;
 		for (int c : counts)
 			total += (unsigned long long)c;
 		printf("frames: %zu, a median over %.2f frames in the mean\n", m, (double)total / (double)m);
-	} catch (const std::exception& e) {
-		fprintf(stderr, "zen-repsim: %s\n", e.what());
-		status = 1;
-	}
-	zen_hip_repsim_destroy(rs);
-	zen_hip_free(dev);
-	zen_hip_free(counts_dev);
-	if (status == 0) { // as `zen`: a red zone found overwritten is an error of its own
-		zen_hip_memcheck_report rep;
-		if (zen_hip_memcheck(&rep) == ZEN_HIP_OK && rep.corrupt_words) {
-			fprintf(stderr, "zen-repsim: memory check: %s\n", rep.first_message);
-			status = 86;
-		}
-	}
-	return status;
+	};
+	return zen::demo::run("zen-repsim", body, [&] {
+		zen_hip_repsim_destroy(rs);
+		zen_hip_free(dev);
+		zen_hip_free(counts_dev);
+	});
 }

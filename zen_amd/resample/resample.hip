@@ -140,15 +140,12 @@ bool poly_switched_off()
 
 } // namespace
 
-struct zen_hip_resample {
+struct zen_hip_resample : Handle<K_COUNT> {
 	Geometry g = {};
 	bool poly = false;
-	hipStream_t stream = nullptr;
 	float* table = nullptr; // (L + 1) rows of Tp floats
 	float* rows = nullptr;  // poly: num rows of Tp floats
 	u64 calls = 0, n_rows = 0, outputs = 0, poly_calls = 0, interp_calls = 0;
-	DeviceTally mem;
-	Profiler<K_COUNT> prof;
 };
 
 namespace {
@@ -224,19 +221,6 @@ int run(zen_hip_resample* h, const float* in, size_t in_stride, u64 in_first, si
 	return ZEN_HIP_OK;
 }
 
-// The host call's rows between host and device memory: plain copies only -- one where both sides lie tight, one per row
-// otherwise.
-int copy_rows(zen_hip_resample* h, float* dst, size_t dst_stride, const float* src, size_t src_stride, size_t cnt, size_t rows, hipMemcpyKind kind)
-{
-	if (dst_stride == cnt && src_stride == cnt) {
-		ZA_HIP(hipMemcpyAsync(dst, src, sizeof(float) * cnt * rows, kind, h->stream));
-		return ZEN_HIP_OK;
-	}
-	for (size_t r = 0; r < rows; ++r)
-		ZA_HIP(hipMemcpyAsync(dst + r * dst_stride, src + r * src_stride, sizeof(float) * cnt, kind, h->stream));
-	return ZEN_HIP_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -291,21 +275,12 @@ int zen_hip_resample_destroy(zen_hip_resample_t h)
 	if (!h)
 		return ZEN_HIP_OK;
 	(void)hipStreamSynchronize(h->stream);
-	(void)zen_hip_free(h->table);
-	(void)zen_hip_free(h->rows);
-	h->prof.release();
+	h->release({h->table, h->rows});
 	delete h;
 	return ZEN_HIP_OK;
 }
 
-int zen_hip_resample_set_stream(zen_hip_resample_t h, void* stream)
-{
-	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "resample_set_stream: null handle");
-	ZA_HIP(hipStreamSynchronize(h->stream));
-	h->stream = (hipStream_t)stream;
-	return ZEN_HIP_OK;
-}
+int zen_hip_resample_set_stream(zen_hip_resample_t h, void* stream) { return set_stream(h, stream, "resample"); }
 
 int zen_hip_resample_run_device(zen_hip_resample_t h, const float* in_dev, size_t in_stride, unsigned long long in_first, size_t in_count,
                                 unsigned long long n_total, unsigned long long out_first, size_t out_count, float* out_dev, size_t out_stride,
@@ -333,11 +308,11 @@ int zen_hip_resample_run_host(zen_hip_resample_t h, const float* in_host, size_t
 		rc = ZEN_HIP_E_HIP;
 	}
 	if (rc == ZEN_HIP_OK)
-		rc = copy_rows(h, d_in, n, in_host, in_stride, n, n_rows, hipMemcpyHostToDevice);
+		rc = h->copy_rows_1d(d_in, n, in_host, in_stride, n, n_rows, hipMemcpyHostToDevice);
 	if (rc == ZEN_HIP_OK)
 		rc = run(h, d_in, n, 0, n, n, 0, n_out, d_out, n_out, n_rows);
 	if (rc == ZEN_HIP_OK)
-		rc = copy_rows(h, out_host, out_stride, d_out, n_out, n_out, n_rows, hipMemcpyDeviceToHost);
+		rc = h->copy_rows_1d(out_host, out_stride, d_out, n_out, n_out, n_rows, hipMemcpyDeviceToHost);
 	const hipError_t es = hipStreamSynchronize(h->stream); // whatever happened, nothing of this call stays in flight
 	(void)zen_hip_free(d_in);
 	(void)zen_hip_free(d_out);
@@ -360,20 +335,12 @@ int zen_hip_resample_stats(zen_hip_resample_t h, zen_hip_resample_stats_t* out)
 	return ZEN_HIP_OK;
 }
 
-int zen_hip_resample_profile(zen_hip_resample_t h, int enable)
-{
-	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
-	h->prof.on = enable != 0;
-	return ZEN_HIP_OK;
-}
+int zen_hip_resample_profile(zen_hip_resample_t h, int enable) { return profile(h, enable); }
 
 int zen_hip_resample_profile_get(zen_hip_resample_t h, double ms[ZEN_HIP_RESAMPLE_KERNELS], unsigned long long bytes[ZEN_HIP_RESAMPLE_KERNELS],
                                  unsigned long long launches[ZEN_HIP_RESAMPLE_KERNELS])
 {
-	if (!h || !ms || !bytes || !launches)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "resample_profile_get: null argument");
-	return h->prof.drain(ms, bytes, launches);
+	return profile_get(h, ms, bytes, launches, "resample");
 }
 
 int zen_hip_resample_n_out(unsigned long long num, unsigned long long den, unsigned long long n_total, unsigned long long* n_out)

@@ -18,21 +18,18 @@
 #include <string>
 #include <vector>
 
+#include "demo.h"
 #include "wav.h"
 #include "zen_hip.h"
 #include "zen_hip_resample.h"
 #include "zen_hip_tsm.h"
 
+using zen::demo::option;
+
 namespace {
 
-void check(int rc, const char* what, const char* msg)
-{
-	if (rc != ZEN_HIP_OK)
-		throw std::runtime_error(std::string(what) + ": " + msg);
-}
-#define ZEN(call) check((call), #call, zen_hip_last_error())
-#define TSM(call) check((call), #call, zen_hip_tsm_last_error())
-#define RES(call) check((call), #call, zen_hip_resample_last_error())
+#define TSM(call) ZEN_LIB(zen_hip_tsm_last_error, call)
+#define RES(call) ZEN_LIB(zen_hip_resample_last_error, call)
 
 int usage()
 {
@@ -56,39 +53,33 @@ int main(int argc, char** argv)
 	float beta = 2.5f;
 	bool plain = false, have_shift = false;
 	for (int i = 1; i < argc; ++i) {
-		char* end = nullptr;
 		if (!strcmp(argv[i], "-o") && i + 1 < argc) {
 			outfile = argv[++i];
 		} else if (!strcmp(argv[i], "-s") && i + 1 < argc) {
-			semitones = strtod(argv[++i], &end);
 			have_shift = true;
-			if (*end)
+			if (!option(argv[++i], &semitones))
 				return usage();
 		} else if (!strcmp(argv[i], "--rate") && i + 1 < argc) {
-			rate = strtoull(argv[++i], &end, 10);
-			if (*end || rate == 0)
+			if (!option(argv[++i], &rate) || rate == 0)
 				return usage();
 		} else if (!strcmp(argv[i], "--quality") && i + 1 < argc) {
-			quality = (int)strtol(argv[++i], &end, 10);
-			if (*end)
+			long q = 0;
+			if (!option(argv[++i], &q))
 				return usage();
+			quality = (int)q;
 		} else if (!strcmp(argv[i], "--plain")) {
 			plain = true;
 		} else if (!strcmp(argv[i], "--nfft") && i + 1 < argc) {
-			nfft = (size_t)strtoull(argv[++i], &end, 10);
-			if (*end)
+			if (!option(argv[++i], &nfft))
 				return usage();
 		} else if (!strcmp(argv[i], "--nfft-ola") && i + 1 < argc) {
-			nfft_ola = (size_t)strtoull(argv[++i], &end, 10);
-			if (*end)
+			if (!option(argv[++i], &nfft_ola))
 				return usage();
 		} else if (!strcmp(argv[i], "--hpr-hop") && i + 1 < argc) {
-			hpr_hop = (size_t)strtoull(argv[++i], &end, 10);
-			if (*end)
+			if (!option(argv[++i], &hpr_hop))
 				return usage();
 		} else if (!strcmp(argv[i], "--beta") && i + 1 < argc) {
-			beta = strtof(argv[++i], &end);
-			if (*end)
+			if (!option(argv[++i], &beta))
 				return usage();
 		} else if (argv[i][0] == '-' || !infile.empty()) {
 			return usage();
@@ -103,27 +94,19 @@ int main(int argc, char** argv)
 	zen_hip_tsm_t ts = nullptr;
 	zen_hip_resample_t rs = nullptr;
 	float *dev = nullptr, *mid = nullptr, *out = nullptr;
-	int status = 0;
-	try {
-		zen::wav::AudioData fd;
-		zen::wav::load(fd, infile);
-		std::vector<float> mono;
-		if (fd.channelCount == 2) {
-			mono.resize(fd.samples.size() / 2);
-			zen::wav::stereo_to_mono(fd.samples.data(), mono.data(), fd.samples.size());
-		} else {
-			mono = fd.samples;
-		}
+	const auto body = [&] {
+		int file_rate = 0;
+		std::vector<float> mono = zen::demo::load_mono(infile, &file_rate);
 		if (mono.empty())
 			throw std::runtime_error("no samples in " + infile);
 		std::vector<float> y;
 		unsigned long long num = 0, den = 0, k = 0;
-		int out_rate = (int)fd.sampleRate;
+		int out_rate = file_rate;
 		if (rate) {
 			// the resampler alone: refused here, before a device is touched, where the ratio is outside its range
 			const size_t n = mono.size();
 			num = rate;
-			den = (unsigned long long)fd.sampleRate;
+			den = (unsigned long long)file_rate;
 			RES(zen_hip_resample_n_out(num, den, n, &k));
 			ZEN(zen_hip_init(0));
 			RES(zen_hip_resample_create(num, den, quality, &rs));
@@ -134,7 +117,7 @@ int main(int argc, char** argv)
 			y.resize((size_t)k);
 			ZEN(zen_hip_memcpy_d2h(y.data(), out, sizeof(float) * k));
 			out_rate = (int)rate;
-			printf("%zu samples at %d Hz in, %llu at %llu Hz out, quality %d\n", n, (int)fd.sampleRate, k, rate, quality);
+			printf("%zu samples at %d Hz in, %llu at %llu Hz out, quality %d\n", n, file_rate, k, rate, quality);
 		} else {
 			const size_t n = (mono.size() + hpr_hop - 1) / hpr_hop * hpr_hop;
 			mono.resize(n, 0.0f);
@@ -146,7 +129,7 @@ int main(int argc, char** argv)
 			RES(zen_hip_resample_n_out(num, den, m, &k));
 			if (k > n)
 				throw std::runtime_error("the length rule of the shift does not hold");
-			const float fs = (float)fd.sampleRate;
+			const float fs = (float)file_rate;
 			if (m > 16383 * (nfft_ola / 2) && nfft_ola >= 16 && nfft_ola < 4096)
 				throw std::runtime_error("the stretched " + std::to_string(m) + " samples are more than 16384 overlap-add frames of " +
 				                         std::to_string(nfft_ola / 2) + ": pick a longer overlap-add frame with --nfft-ola (up to 4096)");
@@ -180,22 +163,13 @@ int main(int argc, char** argv)
 			for (float& v : y)
 				v = v / peak;
 		zen::wav::encode_pcm16_mono(y, out_rate, outfile);
-	} catch (const std::exception& e) {
-		fprintf(stderr, "zen-shift: %s\n", e.what());
-		status = 1;
-	}
-	zen_hip_resample_destroy(rs);
-	zen_hip_tsm_destroy(ts);
-	zen_hip_hpr_destroy(hpr);
-	zen_hip_free(dev);
-	zen_hip_free(mid);
-	zen_hip_free(out);
-	if (status == 0) { // as `zen`: a red zone found overwritten is an error of its own
-		zen_hip_memcheck_report rep;
-		if (zen_hip_memcheck(&rep) == ZEN_HIP_OK && rep.corrupt_words) {
-			fprintf(stderr, "zen-shift: memory check: %s\n", rep.first_message);
-			status = 86;
-		}
-	}
-	return status;
+	};
+	return zen::demo::run("zen-shift", body, [&] {
+		zen_hip_resample_destroy(rs);
+		zen_hip_tsm_destroy(ts);
+		zen_hip_hpr_destroy(hpr);
+		zen_hip_free(dev);
+		zen_hip_free(mid);
+		zen_hip_free(out);
+	});
 }

@@ -31,7 +31,6 @@ static_assert(K_COUNT == ZEN_HIP_TSM_KERNELS, "the header names the kernels");
 constexpr double MIN_ALPHA = 0.25, MAX_ALPHA = 4.0;
 constexpr int MAX_DEVICES = 64;
 
-bool is_pow2(size_t v) { return v && !(v & (v - 1)); }
 bool pv_frame_ok(size_t nfft) { return is_pow2(nfft) && nfft >= 64 && nfft <= 8192; }
 bool ola_frame_ok(size_t nfft) { return is_pow2(nfft) && nfft >= 16 && nfft <= 4096; }
 bool alpha_ok(double a) { return std::isfinite(a) && a >= MIN_ALPHA && a <= MAX_ALPHA; }
@@ -96,12 +95,11 @@ int ensure_tables()
 
 } // namespace
 
-struct zen_hip_tsm {
+struct zen_hip_tsm : Handle<K_COUNT> {
 	float fs = 0.f;
 	size_t N = 0, H = 0, bins = 0, stride = 0, Np = 0, C = 0, max_samples = 0, max_out = 0, max_frames = 0;
 	double max_alpha = 0.0;
 	zen_hip_fft_t fft = nullptr;
-	hipStream_t stream = nullptr;
 	float* rows = nullptr;      // C * max_frames rows of N complex values
 	float* mag = nullptr;       // C * max_frames rows of stride floats
 	uint32_t* theta = nullptr;  // the same shape, as e and psi
@@ -112,17 +110,9 @@ struct zen_hip_tsm {
 	float* stage_in[3] = {nullptr, nullptr, nullptr}; // the host call's device rows: C rows of max_samples samples each
 	float* stage_out = nullptr;                       // C rows of max_out samples
 	unsigned long long calls = 0, clips = 0;
-	DeviceTally mem;
-	Profiler<K_COUNT> prof;
 };
 
 namespace {
-
-template <class T>
-int alloc(zen_hip_tsm* h, T** p, size_t count)
-{
-	return counted_malloc(&h->mem, (void**)p, sizeof(T) * count, "zen_hip_malloc((void**)p, sizeof(T) * count)");
-}
 
 zen_tsm::Framing pv_framing(const zen_hip_tsm* h, double alpha) { return {alpha, (int)h->N, (int)(h->N / 4), 4}; }
 zen_tsm::Framing ola_framing(const zen_hip_tsm* h, double alpha) { return {alpha, (int)h->Np, (int)(h->Np / 2), 2}; }
@@ -241,19 +231,6 @@ int stretch(zen_hip_tsm* h, const float* harm, const float* perc, const float* r
 	return ZEN_HIP_OK;
 }
 
-// The host call's rows, `rows` of `cnt` floats, between host and device memory: plain copies only -- one where both sides lie
-// tight, one per row otherwise.  No two-dimensional copy crosses the link.
-int copy_clips(zen_hip_tsm* h, float* dst, size_t dst_stride, const float* src, size_t src_stride, size_t cnt, size_t rows, hipMemcpyKind kind)
-{
-	if (dst_stride == cnt && src_stride == cnt) {
-		ZA_HIP(hipMemcpyAsync(dst, src, sizeof(float) * cnt * rows, kind, h->stream));
-		return ZEN_HIP_OK;
-	}
-	for (size_t r = 0; r < rows; ++r)
-		ZA_HIP(hipMemcpyAsync(dst + r * dst_stride, src + r * src_stride, sizeof(float) * cnt, kind, h->stream));
-	return ZEN_HIP_OK;
-}
-
 // inspect: `rows` rows of `cnt` words of `width` bytes from the handle's padded rows to the caller's packed ones, both in
 // device memory, the pitches a frame's bins (16 KB at the most)
 int pack_rows(zen_hip_tsm* h, void* dst, size_t dst_stride, const void* src, size_t src_stride, size_t cnt, size_t rows, size_t width)
@@ -315,16 +292,16 @@ int zen_hip_tsm_create(float fs, size_t nfft, size_t nfft_ola, size_t n_clips, s
 			*t++ = ola_divisor_at(i, nfft_ola);
 		ZA_TRY(ensure_tables());
 		ZA_ZEN(zen_hip_fft_create(nfft, &h->fft));
-		ZA_TRY(alloc(h, &h->rows, frames * 2 * nfft));
-		ZA_TRY(alloc(h, &h->mag, frames * S));
-		ZA_TRY(alloc(h, &h->theta, frames * S));
-		ZA_TRY(alloc(h, &h->e, frames * S));
-		ZA_TRY(alloc(h, &h->psi, frames * S));
-		ZA_TRY(alloc(h, &h->owner, frames * S));
-		ZA_TRY(alloc(h, &h->tables, tab.size()));
+		ZA_TRY(h->alloc(&h->rows, frames * 2 * nfft));
+		ZA_TRY(h->alloc(&h->mag, frames * S));
+		ZA_TRY(h->alloc(&h->theta, frames * S));
+		ZA_TRY(h->alloc(&h->e, frames * S));
+		ZA_TRY(h->alloc(&h->psi, frames * S));
+		ZA_TRY(h->alloc(&h->owner, frames * S));
+		ZA_TRY(h->alloc(&h->tables, tab.size()));
 		for (float*& p : h->stage_in)
-			ZA_TRY(alloc(h, &p, n_clips * max_samples));
-		ZA_TRY(alloc(h, &h->stage_out, n_clips * max_out));
+			ZA_TRY(h->alloc(&p, n_clips * max_samples));
+		ZA_TRY(h->alloc(&h->stage_out, n_clips * max_out));
 		ZA_ZEN(zen_hip_memcpy_h2d(h->tables, tab.data(), sizeof(float) * tab.size()));
 		// whatever the transform allocates for its largest batch, up front: one run on zeros
 		ZA_HIP(hipMemsetAsync(h->rows, 0, sizeof(float) * frames * 2 * nfft, h->stream));
@@ -343,22 +320,12 @@ int zen_hip_tsm_destroy(zen_hip_tsm_t h)
 		return ZEN_HIP_OK;
 	(void)hipStreamSynchronize(h->stream);
 	zen_hip_fft_destroy(h->fft);
-	void* bufs[] = {h->rows, h->mag, h->theta, h->e, h->psi, h->owner, h->tables, h->stage_in[0], h->stage_in[1], h->stage_in[2], h->stage_out};
-	for (void* b : bufs)
-		(void)zen_hip_free(b);
-	h->prof.release();
+	h->release({h->rows, h->mag, h->theta, h->e, h->psi, h->owner, h->tables, h->stage_in[0], h->stage_in[1], h->stage_in[2], h->stage_out});
 	delete h;
 	return ZEN_HIP_OK;
 }
 
-int zen_hip_tsm_set_stream(zen_hip_tsm_t h, void* stream)
-{
-	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "tsm_set_stream: null handle");
-	ZA_HIP(hipStreamSynchronize(h->stream));
-	h->stream = (hipStream_t)stream;
-	return ZEN_HIP_OK;
-}
+int zen_hip_tsm_set_stream(zen_hip_tsm_t h, void* stream) { return set_stream(h, stream, "tsm"); }
 
 int zen_hip_tsm_stretch_pv_device(zen_hip_tsm_t h, const float* in_dev, size_t in_stride, size_t n, double alpha, float* out_dev, size_t out_stride)
 {
@@ -392,11 +359,11 @@ int zen_hip_tsm_stretch_hp_host(zen_hip_tsm_t h, const float* harm_host, const f
 	const size_t n_out = samples_out(n, alpha);
 	int rc = ZEN_HIP_OK;
 	for (int i = 0; i < (resid_host ? 3 : 2) && rc == ZEN_HIP_OK; ++i)
-		rc = copy_clips(h, h->stage_in[i], n, (const float*)ins[i], in_stride, n, h->C, hipMemcpyHostToDevice);
+		rc = h->copy_rows_1d(h->stage_in[i], n, (const float*)ins[i], in_stride, n, h->C, hipMemcpyHostToDevice);
 	if (rc == ZEN_HIP_OK)
 		rc = stretch(h, h->stage_in[0], h->stage_in[1], resid_host ? h->stage_in[2] : nullptr, n, n, alpha, h->stage_out, n_out);
 	if (rc == ZEN_HIP_OK)
-		rc = copy_clips(h, out_host, out_stride, h->stage_out, n_out, n_out, h->C, hipMemcpyDeviceToHost);
+		rc = h->copy_rows_1d(out_host, out_stride, h->stage_out, n_out, n_out, h->C, hipMemcpyDeviceToHost);
 	const hipError_t es = hipStreamSynchronize(h->stream); // whatever happened, nothing of this call stays in flight
 	ZA_TRY(rc);
 	ZA_HIP(es);
@@ -458,20 +425,12 @@ int zen_hip_tsm_stats(zen_hip_tsm_t h, zen_hip_tsm_stats_t* out)
 	return ZEN_HIP_OK;
 }
 
-int zen_hip_tsm_profile(zen_hip_tsm_t h, int enable)
-{
-	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "null handle");
-	h->prof.on = enable != 0;
-	return ZEN_HIP_OK;
-}
+int zen_hip_tsm_profile(zen_hip_tsm_t h, int enable) { return profile(h, enable); }
 
 int zen_hip_tsm_profile_get(zen_hip_tsm_t h, double ms[ZEN_HIP_TSM_KERNELS], unsigned long long bytes[ZEN_HIP_TSM_KERNELS],
                             unsigned long long launches[ZEN_HIP_TSM_KERNELS])
 {
-	if (!h || !ms || !bytes || !launches)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "tsm_profile_get: null argument");
-	return h->prof.drain(ms, bytes, launches);
+	return profile_get(h, ms, bytes, launches, "tsm");
 }
 
 int zen_hip_tsm_positions(size_t n, size_t frame, size_t overlap, double alpha, size_t* n_out, size_t* frames, long long* a_out, size_t cap)

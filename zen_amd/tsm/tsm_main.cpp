@@ -16,19 +16,16 @@
 #include <string>
 #include <vector>
 
+#include "demo.h"
 #include "wav.h"
 #include "zen_hip.h"
 #include "zen_hip_tsm.h"
 
+using zen::demo::option;
+
 namespace {
 
-void check(int rc, const char* what, const char* msg)
-{
-	if (rc != ZEN_HIP_OK)
-		throw std::runtime_error(std::string(what) + ": " + msg);
-}
-#define ZEN(call) check((call), #call, zen_hip_last_error())
-#define TSM(call) check((call), #call, zen_hip_tsm_last_error())
+#define TSM(call) ZEN_LIB(zen_hip_tsm_last_error, call)
 
 int usage()
 {
@@ -50,30 +47,24 @@ int main(int argc, char** argv)
 	float beta = 2.5f;
 	bool plain = false;
 	for (int i = 1; i < argc; ++i) {
-		char* end = nullptr;
 		if (!strcmp(argv[i], "-o") && i + 1 < argc) {
 			outfile = argv[++i];
 		} else if (!strcmp(argv[i], "-a") && i + 1 < argc) {
-			alpha = strtod(argv[++i], &end);
-			if (*end)
+			if (!option(argv[++i], &alpha))
 				return usage();
 		} else if (!strcmp(argv[i], "--plain")) {
 			plain = true;
 		} else if (!strcmp(argv[i], "--nfft") && i + 1 < argc) {
-			nfft = (size_t)strtoull(argv[++i], &end, 10);
-			if (*end)
+			if (!option(argv[++i], &nfft))
 				return usage();
 		} else if (!strcmp(argv[i], "--nfft-ola") && i + 1 < argc) {
-			nfft_ola = (size_t)strtoull(argv[++i], &end, 10);
-			if (*end)
+			if (!option(argv[++i], &nfft_ola))
 				return usage();
 		} else if (!strcmp(argv[i], "--hpr-hop") && i + 1 < argc) {
-			hpr_hop = (size_t)strtoull(argv[++i], &end, 10);
-			if (*end)
+			if (!option(argv[++i], &hpr_hop))
 				return usage();
 		} else if (!strcmp(argv[i], "--beta") && i + 1 < argc) {
-			beta = strtof(argv[++i], &end);
-			if (*end)
+			if (!option(argv[++i], &beta))
 				return usage();
 		} else if (argv[i][0] == '-' || !infile.empty()) {
 			return usage();
@@ -86,23 +77,15 @@ int main(int argc, char** argv)
 	zen_hip_hpr_t hpr = nullptr;
 	zen_hip_tsm_t ts = nullptr;
 	float *dev = nullptr, *out = nullptr;
-	int status = 0;
-	try {
-		zen::wav::AudioData fd;
-		zen::wav::load(fd, infile);
-		std::vector<float> mono;
-		if (fd.channelCount == 2) {
-			mono.resize(fd.samples.size() / 2);
-			zen::wav::stereo_to_mono(fd.samples.data(), mono.data(), fd.samples.size());
-		} else {
-			mono = fd.samples;
-		}
+	const auto body = [&] {
+		int rate = 0;
+		std::vector<float> mono = zen::demo::load_mono(infile, &rate);
 		if (mono.empty())
 			throw std::runtime_error("no samples in " + infile);
 		const size_t n = (mono.size() + hpr_hop - 1) / hpr_hop * hpr_hop;
 		mono.resize(n, 0.0f);
 		const size_t n_out = (size_t)floor((double)n * alpha);
-		const float fs = (float)fd.sampleRate;
+		const float fs = (float)rate;
 		if (n_out > 16383 * (nfft_ola / 2) && nfft_ola >= 16 && nfft_ola < 4096)
 			throw std::runtime_error("the output of " + std::to_string(n_out) + " samples is more than 16384 overlap-add frames of " +
 			                         std::to_string(nfft_ola / 2) + ": pick a longer overlap-add frame with --nfft-ola (up to 4096)");
@@ -129,22 +112,13 @@ int main(int argc, char** argv)
 		if (peak > 1.0f)
 			for (float& v : y)
 				v = v / peak;
-		zen::wav::encode_pcm16_mono(y, fd.sampleRate, outfile);
+		zen::wav::encode_pcm16_mono(y, rate, outfile);
 		printf("%zu samples in, %zu out, ratio %g%s\n", n, n_out, alpha, plain ? ", vocoder alone" : "");
-	} catch (const std::exception& e) {
-		fprintf(stderr, "zen-stretch: %s\n", e.what());
-		status = 1;
-	}
-	zen_hip_tsm_destroy(ts);
-	zen_hip_hpr_destroy(hpr);
-	zen_hip_free(dev);
-	zen_hip_free(out);
-	if (status == 0) { // as `zen`: a red zone found overwritten is an error of its own
-		zen_hip_memcheck_report rep;
-		if (zen_hip_memcheck(&rep) == ZEN_HIP_OK && rep.corrupt_words) {
-			fprintf(stderr, "zen-stretch: memory check: %s\n", rep.first_message);
-			status = 86;
-		}
-	}
-	return status;
+	};
+	return zen::demo::run("zen-stretch", body, [&] {
+		zen_hip_tsm_destroy(ts);
+		zen_hip_hpr_destroy(hpr);
+		zen_hip_free(dev);
+		zen_hip_free(out);
+	});
 }
