@@ -10,7 +10,19 @@ zen_hip_pcm_hpri_process at 4096 / 2.5 / 256 / 2.5.  Two comparisons per shape:
         command line tool is: peak_normalise (cli/main.cpp:86-92) and the encoder's loop (cli/wav.h:130-132) over every output,
         and for the offline shape wav.h:77-78's widening loop in front.
 "requirement": the PCM16 median is below the float median by more than the float call's own spread (max - min).
-On the GPU box, under a time limit of its own:  timeout -k 10 900 python tools/ab_pcm_host.py > pcm16_host_ab.json"""
+On the GPU box, under a time limit of its own:  timeout -k 10 900 python tools/ab_pcm_host.py > pcm16_host_ab.json
+
+--fmt i16,i24 (default i16: the record above).  For i24 the same shapes are timed over three routes, interleaved in one process
+on engines of one configuration (A B C A B C ...), PEAK mode, same audio at both depths:
+  i24:   the packed 24-bit call (zen_hip_pcm_*_fmt with ZEN_HIP_PCM_I24 both ways), 3 bytes per sample each way;
+  i16:   the int16 call, 2 bytes per sample each way (both also in GAIN mode, where pieces come down under the kernels
+         of later ones as the float call's do: the like-for-like comparison of the link traffic);
+  float: today's route for a 24-bit file -- wav.h:80-86's unpack-and-widen loop on the host, the float call, then on one host
+         thread the peak search, the scaling, the rounding and the packing of every output (compiled -O2).
+and the two 24-bit kernels are timed alone on one resident piece (HIP events, best of 5) beside the link's own copy of that
+piece's bytes from / to pinned memory and a device-to-device copy of them, all in the same run: "kernels_hidden" says whether
+each kernel's time is below the link's copy time for the piece.  Nothing is asserted: the record states what was measured.
+  timeout -k 10 900 python tools/ab_pcm_host.py --fmt i24 > pcm24_host_ab.json"""
 import argparse
 import ctypes as C
 import json
@@ -48,6 +60,29 @@ extern "C" void host_widen(const int16_t* s, size_t n, float* x)
 {
 	for (std::size_t i = 0; i < n; ++i)
 		x[i] = (float)s[i] / 32767.f;
+}
+extern "C" void host_widen24(const uint8_t* data, size_t n, float* x)              // wav.h:80-86
+{
+	for (std::size_t i = 0; i < n; ++i) {
+		int32_t v = data[3 * i] | (data[3 * i + 1] << 8) | (data[3 * i + 2] << 16);
+		if (v & 0x800000)
+			v |= ~0xFFFFFF;
+		x[i] = (float)v / 8388608.f;
+	}
+}
+extern "C" void host_post24(float* x, size_t n, uint8_t* pcm)                      // peak, scale, round, saturate, pack
+{
+	auto limits = std::minmax_element(x, x + n);
+	const float real_max = std::max(-1 * (*limits.first), *limits.second);
+	for (std::size_t j = 0; j < n; ++j)
+		x[j] /= real_max;
+	for (std::size_t i = 0; i < n; ++i) {
+		long v = lroundf(x[i] * 8388608.f);
+		v = v > 8388607 ? 8388607 : v < -8388608 ? -8388608 : v;
+		pcm[3 * i] = (uint8_t)(v & 255);
+		pcm[3 * i + 1] = (uint8_t)((v >> 8) & 255);
+		pcm[3 * i + 2] = (uint8_t)((v >> 16) & 255);
+	}
 }
 """
 
@@ -186,6 +221,136 @@ def run_shape(name, x, make_engine, outputs, loops, pairs, warmup, offline, pinn
     return res
 
 
+def kernels24_alone(piece):
+    """the two 24-bit kernels on one resident piece of `piece` samples, beside the copies of its 3 * piece bytes: over the link
+    from / to pinned memory, and device to device (HIP events, best of 5, all in this run)"""
+    L = zen_amd.lib.load()
+    packed, f, back = zen_amd.DeviceBuffer(3 * piece, np.uint8), zen_amd.DeviceBuffer(piece), zen_amd.DeviceBuffer(3 * piece, np.uint8)
+    pin = pcm.PinnedPCM(piece, pcm.I24)
+    pin.array[:] = np.random.default_rng(1).integers(0, 256, 3 * piece).astype(np.uint8)
+    packed.upload(pin.array)
+    calls = (("unpack", lambda: pcm.to_float(packed.ptr, 1, piece, f.ptr, fmt=pcm.I24)),
+             ("pack", lambda: pcm.from_float(f.ptr, piece, back.ptr, mode=pcm.GAIN, gain=8388608.0, fmt=pcm.I24)),
+             ("link_up", lambda: zen_amd.lib._ck(L.zen_hip_memcpy_h2d_async(packed.ptr, pin.array.ctypes.data, 3 * piece, None))),
+             ("link_down", lambda: zen_amd.lib._ck(L.zen_hip_memcpy_d2h_async(pin.array.ctypes.data, back.ptr, 3 * piece, None))),
+             ("device_copy", lambda: zen_amd.lib._ck(L.zen_hip_memcpy_d2d(back.ptr, packed.ptr, 3 * piece, None))))
+    out = {}
+    for name, call in calls:
+        best = 1e30
+        for _ in range(6):
+            a, b = zen_amd.Event(), zen_amd.Event()
+            a.record()
+            call()
+            b.record()
+            zen_amd.synchronize()
+            best = min(best, a.elapsed_ms(b))
+        out[name + "_ms"] = best
+    pcm.to_float(packed.ptr, 1, piece, f.ptr, fmt=pcm.I24)
+    pcm.from_float(f.ptr, piece, back.ptr, mode=pcm.GAIN, gain=8388608.0, fmt=pcm.I24)
+    zen_amd.synchronize()
+    identity = bool(np.array_equal(back.download(), packed.download()))
+    for b in (packed, f, back):
+        b.free()
+    pin.free()
+    out.update({"piece_samples": piece, "unpack_then_pack_is_identity": identity,
+                "GBps": {"unpack": 7e-6 * piece / out["unpack_ms"], "pack": 7e-6 * piece / out["pack_ms"],
+                         "link_up": 3e-6 * piece / out["link_up_ms"], "link_down": 3e-6 * piece / out["link_down_ms"],
+                         "device_copy": 6e-6 * piece / out["device_copy_ms"]},
+                "kernels_hidden": bool(out["unpack_ms"] < out["link_up_ms"] and out["pack_ms"] < out["link_down_ms"])})
+    return out
+
+
+def run_shape_i24(name, x, make_engine, outputs, loops, pairs, warmup, offline, pinned):
+    """the three routes of a 24-bit caller, PEAK mode; the int16 route on the same audio at 16 bits"""
+    n = x.size
+    v24 = np.clip(np.round(x * 8388607.0), -8388608, 8388607).astype(np.int32)
+    keep = []
+
+    def buf(m, fmt):
+        if fmt is None:
+            p = zen_amd.PinnedHost(m) if pinned else None
+            a = p.array if pinned else np.zeros(m, np.float32)
+        else:
+            p = pcm.PinnedPCM(m, fmt) if pinned else None
+            a = p.array if pinned else np.zeros(m * (3 if fmt == pcm.I24 else 1), np.uint8 if fmt == pcm.I24 else np.int16)
+        if p is not None:
+            keep.append(p)
+        return a
+    x24, x16, xf = buf(n, pcm.I24), buf(n, pcm.I16), buf(n, None)
+    x24[:] = pcm.pack24(v24)
+    x16[:] = (v24 >> 8).astype(np.int16)
+    o24 = {k: buf(n, pcm.I24) for k in outputs}
+    o16 = {k: buf(n, pcm.I16) for k in outputs}
+    fo = {k: buf(n, None) for k in outputs}
+    enc = {k: np.zeros(3 * n, np.uint8) for k in outputs if not (offline and k == "resid")}     # the encoder's own (pageable) bytes
+    eng = {r: make_engine() for r in ("i24", "i16", "float")}
+    p = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    if offline:
+        def call_pcm(e, xin, o, mode=pcm.PEAK, gain=1.0):
+            return pcm.hpri_process(e, xin, harm=o.get("harm"), perc=o.get("perc"), resid=o.get("resid"), mode=mode, gain=gain)
+
+        def call_float():
+            eng["float"].process(xf, out=(fo.get("harm"), fo.get("perc"), fo.get("resid")))
+    else:
+        def call_pcm(e, xin, o, mode=pcm.PEAK, gain=1.0):
+            return pcm.hpr_process_host(e, xin, mode=mode, gain=gain, **o)
+
+        def call_float():
+            eng["float"].process_host(xf, **fo)
+
+    def route_float():
+        t = {"widen": ms(lambda: loops.host_widen24(p(x24), C.c_size_t(n), p(xf))), "call": ms(call_float), "post": 0.0}
+        for k in enc:
+            t["post"] += ms(lambda: loops.host_post24(p(fo[k]), C.c_size_t(n), p(enc[k])))
+        return t
+    for _ in range(warmup):
+        call_pcm(eng["i24"], x24, o24, pcm.GAIN)
+        call_pcm(eng["i16"], x16, o16, pcm.GAIN)
+        peaks = call_pcm(eng["i24"], x24, o24)
+        call_pcm(eng["i16"], x16, o16)
+        route_float()
+    top = max(float(np.max(peaks)), 1e-30)
+    t = {"i24": [], "i16": [], "i24_gain": [], "i16_gain": [], "float_widen": [], "float_call": [], "float_post": []}
+    stats = None
+    for _ in range(pairs):
+        t["i24_gain"].append(ms(lambda: call_pcm(eng["i24"], x24, o24, pcm.GAIN, 8388608.0 / top)))
+        stats_gain = pcm.host_stats()
+        t["i16_gain"].append(ms(lambda: call_pcm(eng["i16"], x16, o16, pcm.GAIN, 32767.0 / top)))
+        t["i24"].append(ms(lambda: call_pcm(eng["i24"], x24, o24)))
+        stats = pcm.host_stats()
+        t["i16"].append(ms(lambda: call_pcm(eng["i16"], x16, o16)))
+        r = route_float()
+        for k in ("widen", "call", "post"):
+            t["float_" + k].append(r[k])
+    same = all(bool(np.array_equal(enc[k], o24[k])) for k in enc)
+    n_down = len(enc)
+    s24, s16, sfc = summary(t["i24"]), summary(t["i16"]), summary(t["float_call"])
+    g24, g16 = summary(t["i24_gain"]), summary(t["i16_gain"])
+    whole = summary([a + b + c for a, b, c in zip(t["float_widen"], t["float_call"], t["float_post"])])
+    res = {"shape": name, "fmt": "i24", "mode": "peak", "buffers": "pinned" if pinned else "pageable", "samples": n, "outputs": list(outputs),
+           "pieces": stats["n_pieces"], "piece_frames": stats["piece_frames"], "peak_tail_ms": stats["tail_ms"],
+           "pieces_gain": stats_gain["n_pieces"], "piece_frames_gain": stats_gain["piece_frames"],
+           "i24_call": s24, "i16_call": s16, "i24_gain_call": g24, "i16_gain_call": g16, "float_call_alone": sfc, "host_widen24": summary(t["float_widen"]),
+           "host_peak_scale_round_pack": summary(t["float_post"]), "float_route": whole,
+           "ratio_i24_over_i16": s24["median_ms"] / s16["median_ms"], "ratio_float_call_over_i24": sfc["median_ms"] / s24["median_ms"],
+           "ratio_float_route_over_i24": whole["median_ms"] / s24["median_ms"],
+           "expect_i24_below_float_call_alone": bool(s24["median_ms"] < sfc["median_ms"]),
+           "gain_ratio_i24_over_i16": g24["median_ms"] / g16["median_ms"], "gain_ratio_float_call_over_i24": sfc["median_ms"] / g24["median_ms"],
+           "gain_expect_i24_below_float_call_alone": bool(g24["median_ms"] < sfc["median_ms"]),
+           "i24_equals_host_route_bytes": same,
+           "link_GBps": {"i24_up": 3e-6 * n / s24["median_ms"], "i24_down": 3e-6 * n * n_down / s24["median_ms"],
+                         "i16_up": 2e-6 * n / s16["median_ms"], "i16_down": 2e-6 * n * n_down / s16["median_ms"],
+                         "float_up": 4e-6 * n / sfc["median_ms"], "float_down": 4e-6 * n * n_down / sfc["median_ms"],
+                         "of_GBps_each_way": LINK_GBPS},
+           "kernels_alone_on_a_piece": kernels24_alone(int(stats["piece_frames"]))}
+    for e in ("i24", "i16"):
+        pcm.release(eng[e])
+    eng.clear()
+    for k in keep:
+        k.free()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=7)
@@ -194,13 +359,16 @@ def main():
     ap.add_argument("--hops", type=int, default=25840)
     ap.add_argument("--shapes", default="block_perc,block_all,offline")
     ap.add_argument("--buffers", default="pinned,pageable")
+    ap.add_argument("--fmt", default="i16", help="i16, i24 or both: which caller's routes are timed")
     a = ap.parse_args()
     assert a.pairs >= 5
     zen_amd.init(0)
     pcm.load()
     loops = host_loops()
     ALL = zen_amd.OUTPUT_HARMONIC | zen_amd.OUTPUT_PERCUSSIVE | zen_amd.OUTPUT_RESIDUAL
-    results = []
+    results, results24 = [], []
+    fmts = a.fmt.split(",")
+    assert fmts and all(f in ("i16", "i24") for f in fmts)
     for shape in a.shapes.split(","):
         if shape == "offline":
             n = int(a.seconds * FS)
@@ -213,14 +381,26 @@ def main():
             mk = (lambda flags=flags: zen_amd.HPR(FS, 1024, 2.0, flags, zen_amd.TIME_CAUSAL, True, 1, 0))
             outs, off = (("perc",) if shape == "block_perc" else ("harm", "perc", "resid")), False
         for buf in a.buffers.split(","):
+            if "i24" in fmts:
+                r = run_shape_i24(shape, x, mk, outs, loops, a.pairs, a.warmup, off, buf == "pinned")
+                results24.append(r)
+                print("# i24 %s %s: i24 %.2f ms, i16 %.2f ms, float call %.2f ms, float route %.2f ms" % (
+                    shape, buf, r["i24_call"]["median_ms"], r["i16_call"]["median_ms"], r["float_call_alone"]["median_ms"],
+                    r["float_route"]["median_ms"]), file=sys.stderr, flush=True)
+            if "i16" not in fmts:
+                continue
             results.append(run_shape(shape, x, mk, outs, loops, a.pairs, a.warmup, off, buf == "pinned"))
             print("# %s %s: float %.2f ms, pcm gain %.2f ms, float+host %.2f ms, pcm peak %.2f ms" % (
                 shape, buf, results[-1]["float"]["median_ms"], results[-1]["pcm_gain"]["median_ms"],
                 results[-1]["float_plus_host"]["median_ms"], results[-1]["pcm_peak"]["median_ms"]), file=sys.stderr, flush=True)
     pinned = [r for r in results if r["buffers"] == "pinned"]
-    print(json.dumps({"tool": "tools/ab_pcm_host.py", "device": zen_amd.device_name(), "pairs": a.pairs, "warmup": a.warmup,
-                      "requirement_met_pinned": bool(pinned and all(r["requirement_gain"] and r["requirement_peak"] for r in pinned)),
-                      "results": results}))
+    record = {"tool": "tools/ab_pcm_host.py", "device": zen_amd.device_name(), "pairs": a.pairs, "warmup": a.warmup}
+    if "i16" in fmts:
+        record.update({"requirement_met_pinned": bool(pinned and all(r["requirement_gain"] and r["requirement_peak"] for r in pinned)),
+                       "results": results})
+    if "i24" in fmts:
+        record["results_i24"] = results24
+    print(json.dumps(record))
 
 
 if __name__ == "__main__":

@@ -11,6 +11,12 @@ hipError_t launch_to_float(const int16_t* src, int channels, size_t n_frames, fl
 hipError_t launch_peak(const float* src, size_t n, float* minmax, hipStream_t s);
 // mode: ZEN_PCM_MODE_PEAK (divides by max(-minmax[0], minmax[1])) or ZEN_PCM_MODE_GAIN (multiplies by gain)
 hipError_t launch_from_float(const float* src, size_t n, int mode, float gain, const float* minmax, int16_t* dst, hipStream_t s);
+// the same two for packed 24-bit samples (three little-endian bytes each, no alignment asked of the packed side)
+hipError_t launch_to_float24(const uint8_t* src, int channels, size_t n_frames, float* dst, hipStream_t s);
+hipError_t launch_from_float24(const float* src, size_t n, int mode, float gain, const float* minmax, uint8_t* dst, hipStream_t s);
+// by format (ZEN_PCM_FMT_I16 or ZEN_PCM_FMT_I24, checked by the caller): the pipeline's two launch sites
+hipError_t launch_unpack(int fmt, const void* src, int channels, size_t n_frames, float* dst, hipStream_t s);
+hipError_t launch_pack(int fmt, const float* src, size_t n, int mode, float gain, const float* minmax, void* dst, hipStream_t s);
 // `pairs` (<= 64) pairs of (+inf, -inf) at minmax
 hipError_t launch_minmax_init(float* minmax, int pairs, hipStream_t s);
 

@@ -1,5 +1,5 @@
-// pcm_pipe.hip -- the C ABI of libzen_hip_pcm.so (zen_hip_pcm.h): the three kernels on device pointers, and the two
-// host-to-host calls that put them between 2-byte copies and the float engines of libzen_hip.so.
+// pcm_pipe.hip -- the C ABI of libzen_hip_pcm.so (zen_hip_pcm.h): the kernels on device pointers, and the two
+// host-to-host calls that put them between 2- or 3-byte copies and the float engines of libzen_hip.so.
 //
 // One pipeline, two callers.  run_pieces is the three-stream pattern of zen_hip_hpr_process_host / zen_hip_hpri_process
 // (csrc/hpr.hip, csrc/hpri.hip) on top of the engines' public C ABI: piece k+1 goes up and is widened on the upload stream,
@@ -43,14 +43,14 @@ enum { KIND_HPR = 0, KIND_HPRI = 1 };
 struct Ctx {
 	int kind = KIND_HPR;
 	hipStream_t run = nullptr, s_in = nullptr, s_out = nullptr; // run: the stream the engine is put on
-	int16_t* in16 = nullptr;
-	size_t in16_cap = 0; // int16 elements
+	uint8_t* inb = nullptr; // the input as it came up, in its format
+	size_t inb_cap = 0;     // bytes
 	float* fin = nullptr;
 	size_t fin_cap = 0;
 	float* fout[3] = {nullptr, nullptr, nullptr}; // harmonic, percussive, residual
 	size_t fout_cap[3] = {0, 0, 0};
-	int16_t* out16[3] = {nullptr, nullptr, nullptr};
-	size_t out16_cap[3] = {0, 0, 0};
+	uint8_t* outb[3] = {nullptr, nullptr, nullptr}; // the outputs in their format, on their way down
+	size_t outb_cap[3] = {0, 0, 0};                 // bytes
 	float* minmax = nullptr;                             // 3 x (min, max) on the device
 	float *minmax_host = nullptr, *minmax_host_dev = nullptr; // their pinned landing place
 	std::vector<hipEvent_t> ev;
@@ -121,11 +121,11 @@ void free_ctx(Ctx* c)
 		(void)hipStreamSynchronize(c->s_in);
 	if (c->s_out)
 		(void)hipStreamSynchronize(c->s_out);
-	(void)zen_hip_free(c->in16);
+	(void)zen_hip_free(c->inb);
 	(void)zen_hip_free(c->fin);
 	for (int o = 0; o < 3; ++o) {
 		(void)zen_hip_free(c->fout[o]);
-		(void)zen_hip_free(c->out16[o]);
+		(void)zen_hip_free(c->outb[o]);
 	}
 	(void)zen_hip_free(c->minmax);
 	if (c->minmax_host)
@@ -156,9 +156,9 @@ bool any_overlap(const Span* s, int count)
 }
 
 // the never-written residual of HPRIOffline: zeros, by a few host threads beside the pipeline (as csrc/hpri.hip does)
-void zero_host(int16_t* dst, size_t n)
+void zero_host(uint8_t* dst, size_t bytes)
 {
-	const size_t bytes = n * sizeof(int16_t), piece = (size_t)64 << 20;
+	const size_t n = bytes, piece = (size_t)64 << 20;
 	unsigned k = (unsigned)(bytes / piece);
 	const unsigned hw = std::thread::hardware_concurrency();
 	if (k > 8)
@@ -177,7 +177,7 @@ void zero_host(int16_t* dst, size_t n)
 		if (a >= b)
 			break;
 		try {
-			th.emplace_back([=] { memset(dst + a, 0, (b - a) * sizeof(int16_t)); });
+			th.emplace_back([=] { memset(dst + a, 0, b - a); });
 			done_to = b;
 		}
 		catch (...) {
@@ -185,9 +185,16 @@ void zero_host(int16_t* dst, size_t n)
 		}
 	}
 	if (done_to < n)
-		memset(dst + done_to, 0, (n - done_to) * sizeof(int16_t));
+		memset(dst + done_to, 0, n - done_to);
 	for (auto& t : th)
 		t.join();
+}
+
+int check_fmt(const char* who, const char* which, int fmt)
+{
+	if (!pcm_sample_bytes(fmt))
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: %s format must be ZEN_HIP_PCM_I16 or ZEN_HIP_PCM_I24 (got %d)", who, which, fmt);
+	return ZEN_HIP_OK;
 }
 
 int check_mode_channels(const char* who, int channels, int mode)
@@ -201,10 +208,11 @@ int check_mode_channels(const char* who, int channels, int mode)
 
 // ---- the piece pipeline ----------------------------------------------------------------------------------------------------
 struct Job {
-	const int16_t* in_host;
+	int in_fmt, out_fmt; // ZEN_HIP_PCM_I16 / _I24, each side on its own
+	const uint8_t* in_host;
 	int channels, mode;
 	size_t n, piece;   // samples of the call and of a piece (the last piece may be shorter)
-	int16_t* hosts[3]; // harmonic, percussive, residual; NULL: not wanted, or not the pipeline's to write (HPRIOffline's residual)
+	uint8_t* hosts[3]; // harmonic, percussive, residual; NULL: not wanted, or not the pipeline's to write (HPRIOffline's residual)
 	float gain, *peaks; // peaks: NULL, or where PEAK mode writes the three peaks
 };
 
@@ -217,25 +225,26 @@ int run_pieces(void* h, int kind, const Job& j, Bind bind, InEnd in_end, Engine 
 {
 	const double t_start = now_ms();
 	const size_t n = j.n, ch = (size_t)j.channels, n_pieces = ceil_div(n, j.piece);
-	int16_t* const* hosts = j.hosts;
+	const size_t in_fb = (size_t)pcm_sample_bytes(j.in_fmt) * ch, out_sb = (size_t)pcm_sample_bytes(j.out_fmt); // bytes of an input frame, an output sample
+	uint8_t* const* hosts = j.hosts;
 	const bool peak_mode = j.mode == ZEN_HIP_PCM_PEAK;
 	Ctx* c = nullptr;
 	ZA_TRY(ctx_for(h, kind, &c));
 	ZA_ZEN_AS(bind(c->run), "the engine's set_stream");
-	ZA_TRY(grow(c, c->in16, c->in16_cap, n * ch));
+	ZA_TRY(grow(c, c->inb, c->inb_cap, n * in_fb));
 	ZA_TRY(grow(c, c->fin, c->fin_cap, n));
 	for (int o = 0; o < 3; ++o)
 		if (hosts[o]) {
 			ZA_TRY(grow(c, c->fout[o], c->fout_cap[o], n));
-			ZA_TRY(grow(c, c->out16[o], c->out16_cap[o], n));
+			ZA_TRY(grow(c, c->outb[o], c->outb_cap[o], n * out_sb));
 		}
 	// events: [k] piece k is up and widened, [n_pieces + k] piece k is through the engine (PEAK: and folded into min / max),
 	// [2 n_pieces + k] PEAK: piece k is narrowed, [3 n_pieces] PEAK: the peaks are known
 	ZA_TRY(need_events(c, 3 * n_pieces + 1));
 	Registered reg_in, reg_out[3];
-	reg_in.take(j.in_host, 2 * ch * n, true);
+	reg_in.take(j.in_host, in_fb * n, true);
 	for (int o = 0; o < 3; ++o)
-		reg_out[o].take(hosts[o], 2 * n, true);
+		reg_out[o].take(hosts[o], out_sb * n, true);
 	memset(&t_stats, 0, sizeof(t_stats));
 	t_stats.n_pieces = n_pieces;
 	t_stats.piece_frames = j.piece;
@@ -254,8 +263,8 @@ int run_pieces(void* h, int kind, const Job& j, Bind bind, InEnd in_end, Engine 
 		if (end > n)
 			end = n;
 		if (end > uploaded) {
-			ZA_HIP(hipMemcpyAsync(c->in16 + uploaded * ch, j.in_host + uploaded * ch, 2 * ch * (end - uploaded), hipMemcpyHostToDevice, c->s_in));
-			ZA_HIP(zen_pcm::launch_to_float(c->in16 + uploaded * ch, j.channels, end - uploaded, c->fin + uploaded, c->s_in));
+			ZA_HIP(hipMemcpyAsync(c->inb + uploaded * in_fb, j.in_host + uploaded * in_fb, in_fb * (end - uploaded), hipMemcpyHostToDevice, c->s_in));
+			ZA_HIP(zen_pcm::launch_unpack(j.in_fmt, c->inb + uploaded * in_fb, j.channels, end - uploaded, c->fin + uploaded, c->s_in));
 			uploaded = end;
 		}
 		ZA_HIP(hipEventRecord(c->ev[k], c->s_in));
@@ -267,14 +276,14 @@ int run_pieces(void* h, int kind, const Job& j, Bind bind, InEnd in_end, Engine 
 		ZA_HIP(hipStreamWaitEvent(narrow_on, after, 0));
 		for (int o = 0; o < 3; ++o)
 			if (hosts[o])
-				ZA_HIP(zen_pcm::launch_from_float(c->fout[o] + b, e - b, j.mode, j.gain, c->minmax + 2 * o, c->out16[o] + b, narrow_on));
+				ZA_HIP(zen_pcm::launch_pack(j.out_fmt, c->fout[o] + b, e - b, j.mode, j.gain, c->minmax + 2 * o, c->outb[o] + b * out_sb, narrow_on));
 		if (narrow_on != c->s_out) {
 			ZA_HIP(hipEventRecord(c->ev[2 * n_pieces + k], narrow_on));
 			ZA_HIP(hipStreamWaitEvent(c->s_out, c->ev[2 * n_pieces + k], 0));
 		}
 		for (int o = 0; o < 3; ++o)
 			if (hosts[o])
-				ZA_HIP(hipMemcpyAsync(hosts[o] + b, c->out16[o] + b, 2 * (e - b), hipMemcpyDeviceToHost, c->s_out));
+				ZA_HIP(hipMemcpyAsync(hosts[o] + b * out_sb, c->outb[o] + b * out_sb, out_sb * (e - b), hipMemcpyDeviceToHost, c->s_out));
 		return ZEN_HIP_OK;
 	};
 	bool tail_marked = false;
@@ -331,24 +340,63 @@ int run_pieces(void* h, int kind, const Job& j, Bind bind, InEnd in_end, Engine 
 } // namespace
 
 static_assert(ZEN_HIP_PCM_PEAK == ZEN_PCM_MODE_PEAK && ZEN_HIP_PCM_GAIN == ZEN_PCM_MODE_GAIN, "public and kernel-side mode values agree");
+static_assert(ZEN_HIP_PCM_I16 == ZEN_PCM_FMT_I16 && ZEN_HIP_PCM_I24 == ZEN_PCM_FMT_I24, "public and kernel-side format values agree");
+
+namespace {
+
+// the bodies of the kernel entry points; `who`: the caller's name in the messages (the int16 calls keep theirs)
+int unpack_dev(const char* who, int fmt, const void* src_dev, int channels, size_t n_frames, float* dst_dev, void* stream)
+{
+	ZA_TRY(check_fmt(who, "sample", fmt));
+	if (channels != 1 && channels != 2)
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: channels must be 1 or 2 (got %d)", who, channels);
+	if (n_frames == 0)
+		return ZEN_HIP_OK;
+	if (!src_dev || !dst_dev)
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: null argument", who);
+	if ((fmt == ZEN_HIP_PCM_I16 && ((uintptr_t)src_dev & 1)) || ((uintptr_t)dst_dev & 3))
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: int16_t pointers need 2-byte, float pointers 4-byte alignment", who);
+	ZA_HIP(zen_pcm::launch_unpack(fmt, src_dev, channels, n_frames, dst_dev, (hipStream_t)stream));
+	return ZEN_HIP_OK;
+}
+
+int pack_dev(const char* who, int fmt, const float* src_dev, size_t n, int mode, float gain, const float* minmax_dev, void* dst_dev, void* stream)
+{
+	ZA_TRY(check_fmt(who, "sample", fmt));
+	if (mode != ZEN_HIP_PCM_PEAK && mode != ZEN_HIP_PCM_GAIN)
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: mode must be ZEN_HIP_PCM_PEAK or ZEN_HIP_PCM_GAIN (got %d)", who, mode);
+	if (n == 0)
+		return ZEN_HIP_OK;
+	if (!src_dev || !dst_dev || (mode == ZEN_HIP_PCM_PEAK && !minmax_dev))
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: null argument", who);
+	if (((uintptr_t)src_dev & 3) || (fmt == ZEN_HIP_PCM_I16 && ((uintptr_t)dst_dev & 1)) || ((uintptr_t)minmax_dev & 3))
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: int16_t pointers need 2-byte, float pointers 4-byte alignment", who);
+	ZA_HIP(zen_pcm::launch_pack(fmt, src_dev, n, mode, gain, minmax_dev, dst_dev, (hipStream_t)stream));
+	return ZEN_HIP_OK;
+}
+
+int hpr_host(const char* who, zen_hip_hpr_t h, int in_fmt, const void* in_host, int channels, size_t n_hops, int out_fmt, void* harm, void* perc,
+             void* resid, int mode, float gain, float peaks[3], size_t piece_hops);
+int hpri_host(const char* who, zen_hip_hpri_t h, int in_fmt, const void* audio_host, int channels, size_t n_frames, int out_fmt, void* harm,
+              void* perc, void* resid, int mode, float gain, float peaks[3], size_t range_samples);
+
+} // namespace
 
 extern "C" {
 
 const char* zen_hip_pcm_last_error(void) { return t_err; }
 const char* zen_hip_pcm_version(void) { return "zen_hip_pcm 1 (gfx950)"; }
 
+size_t zen_hip_pcm_sample_bytes(int fmt) { return (size_t)pcm_sample_bytes(fmt); }
+
 int zen_hip_pcm_to_float(const int16_t* src_dev, int channels, size_t n_frames, float* dst_dev, void* stream)
 {
-	if (channels != 1 && channels != 2)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_to_float: channels must be 1 or 2 (got %d)", channels);
-	if (n_frames == 0)
-		return ZEN_HIP_OK;
-	if (!src_dev || !dst_dev)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_to_float: null argument");
-	if (((uintptr_t)src_dev & 1) || ((uintptr_t)dst_dev & 3))
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_to_float: int16_t pointers need 2-byte, float pointers 4-byte alignment");
-	ZA_HIP(zen_pcm::launch_to_float(src_dev, channels, n_frames, dst_dev, (hipStream_t)stream));
-	return ZEN_HIP_OK;
+	return unpack_dev("pcm_to_float", ZEN_HIP_PCM_I16, src_dev, channels, n_frames, dst_dev, stream);
+}
+
+int zen_hip_pcm_unpack(int fmt, const void* src_dev, int channels, size_t n_frames, float* dst_dev, void* stream)
+{
+	return unpack_dev("pcm_unpack", fmt, src_dev, channels, n_frames, dst_dev, stream);
 }
 
 int zen_hip_pcm_peak(const float* src_dev, size_t n, float* minmax_dev, void* stream)
@@ -366,16 +414,12 @@ int zen_hip_pcm_peak(const float* src_dev, size_t n, float* minmax_dev, void* st
 int zen_hip_pcm_from_float(const float* src_dev, size_t n, int mode, float gain, const float* minmax_dev, int16_t* dst_dev,
                            void* stream)
 {
-	if (mode != ZEN_HIP_PCM_PEAK && mode != ZEN_HIP_PCM_GAIN)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_from_float: mode must be ZEN_HIP_PCM_PEAK or ZEN_HIP_PCM_GAIN (got %d)", mode);
-	if (n == 0)
-		return ZEN_HIP_OK;
-	if (!src_dev || !dst_dev || (mode == ZEN_HIP_PCM_PEAK && !minmax_dev))
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_from_float: null argument");
-	if (((uintptr_t)src_dev & 3) || ((uintptr_t)dst_dev & 1) || ((uintptr_t)minmax_dev & 3))
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_from_float: int16_t pointers need 2-byte, float pointers 4-byte alignment");
-	ZA_HIP(zen_pcm::launch_from_float(src_dev, n, mode, gain, minmax_dev, dst_dev, (hipStream_t)stream));
-	return ZEN_HIP_OK;
+	return pack_dev("pcm_from_float", ZEN_HIP_PCM_I16, src_dev, n, mode, gain, minmax_dev, dst_dev, stream);
+}
+
+int zen_hip_pcm_pack(int fmt, const float* src_dev, size_t n, int mode, float gain, const float* minmax_dev, void* dst_dev, void* stream)
+{
+	return pack_dev("pcm_pack", fmt, src_dev, n, mode, gain, minmax_dev, dst_dev, stream);
 }
 
 int zen_hip_pcm_host_stats_get(zen_hip_pcm_host_stats* out)
@@ -424,20 +468,51 @@ int zen_hip_pcm_release_all(void)
 int zen_hip_pcm_hpr_process_host(zen_hip_hpr_t h, const int16_t* in_host, int channels, size_t n_hops, int16_t* harm, int16_t* perc,
                                  int16_t* resid, int mode, float gain, float peaks[3], size_t piece_hops)
 {
+	return hpr_host("pcm_hpr_process_host", h, ZEN_HIP_PCM_I16, in_host, channels, n_hops, ZEN_HIP_PCM_I16, harm, perc, resid, mode, gain, peaks, piece_hops);
+}
+
+int zen_hip_pcm_hpr_process_host_fmt(zen_hip_hpr_t h, int in_fmt, const void* in_host, int channels, size_t n_hops, int out_fmt, void* harm,
+                                     void* perc, void* resid, int mode, float gain, float peaks[3], size_t piece_hops)
+{
+	return hpr_host("pcm_hpr_process_host_fmt", h, in_fmt, in_host, channels, n_hops, out_fmt, harm, perc, resid, mode, gain, peaks, piece_hops);
+}
+
+int zen_hip_pcm_hpri_process(zen_hip_hpri_t h, const int16_t* audio_host, int channels, size_t n_frames, int16_t* harm, int16_t* perc,
+                             int16_t* resid, int mode, float gain, float peaks[3], size_t range_samples)
+{
+	return hpri_host("pcm_hpri_process", h, ZEN_HIP_PCM_I16, audio_host, channels, n_frames, ZEN_HIP_PCM_I16, harm, perc, resid, mode, gain, peaks, range_samples);
+}
+
+int zen_hip_pcm_hpri_process_fmt(zen_hip_hpri_t h, int in_fmt, const void* audio_host, int channels, size_t n_frames, int out_fmt, void* harm,
+                                 void* perc, void* resid, int mode, float gain, float peaks[3], size_t range_samples)
+{
+	return hpri_host("pcm_hpri_process_fmt", h, in_fmt, audio_host, channels, n_frames, out_fmt, harm, perc, resid, mode, gain, peaks, range_samples);
+}
+
+} // extern "C"
+
+namespace {
+
+int hpr_host(const char* who, zen_hip_hpr_t h, int in_fmt, const void* in_host, int channels, size_t n_hops, int out_fmt, void* harm, void* perc,
+             void* resid, int mode, float gain, float peaks[3], size_t piece_hops)
+{
 	if (!h || !in_host)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpr_process_host: null argument");
-	ZA_TRY(check_mode_channels("pcm_hpr_process_host", channels, mode));
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: null argument", who);
+	ZA_TRY(check_fmt(who, "input", in_fmt));
+	ZA_TRY(check_fmt(who, "output", out_fmt));
+	ZA_TRY(check_mode_channels(who, channels, mode));
 	zen_hip_hpr_params P;
 	ZA_ZEN(zen_hip_hpr_get_params(h, &P));
 	if (P.n_streams != 1)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpr_process_host: one stream per engine (host blocks of several streams: one engine each)");
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: one stream per engine (host blocks of several streams: one engine each)", who);
 	if (n_hops == 0)
 		return ZEN_HIP_OK;
 	const size_t hop = P.hop, n = n_hops * hop, ch = (size_t)channels;
+	const size_t in_sb = (size_t)pcm_sample_bytes(in_fmt), out_sb = (size_t)pcm_sample_bytes(out_fmt);
 	{
-		const Span s[4] = {{(const char*)in_host, 2 * ch * n}, {(const char*)harm, 2 * n}, {(const char*)perc, 2 * n}, {(const char*)resid, 2 * n}};
+		const Span s[4] = {{(const char*)in_host, in_sb * ch * n}, {(const char*)harm, out_sb * n}, {(const char*)perc, out_sb * n}, {(const char*)resid, out_sb * n}};
 		if (any_overlap(s, 4))
-			ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpr_process_host: the host buffers must not overlap (pieces come down while later pieces go up)");
+			ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: the host buffers must not overlap (pieces come down while later pieces go up)", who);
 	}
 	// default pieces: 4 Mi samples in GAIN mode -- 8 MiB on the link per piece and direction, the float path's rule in bytes --
 	// and 8 Mi in PEAK mode, where nothing comes down inside the loop and the pieces only pace the uploads and the tail
@@ -445,7 +520,7 @@ int zen_hip_pcm_hpr_process_host(zen_hip_hpr_t h, const int16_t* in_host, int ch
 	// PEAK 4.22 / 3.32 / 2.84 / 2.49 / 2.39 / 2.37 ms at 0.5 / 1 / 2 / 4 / 8 / 12.6 Mi samples per piece)
 	size_t piece = piece_hops ? piece_hops : ((size_t)(mode == ZEN_HIP_PCM_PEAK ? 8 : 4) << 20) / hop;
 	piece = piece < 1 ? 1 : piece > n_hops ? n_hops : piece;
-	const Job job = {in_host, channels, mode, n, piece * hop, {harm, perc, resid}, gain, peaks};
+	const Job job = {in_fmt, out_fmt, (const uint8_t*)in_host, channels, mode, n, piece * hop, {(uint8_t*)harm, (uint8_t*)perc, (uint8_t*)resid}, gain, peaks};
 	return run_pieces(
 	    h, KIND_HPR, job, [&](hipStream_t run) { return zen_hip_hpr_set_stream(h, run); },
 	    [](size_t, size_t e, size_t* end) { return *end = e, ZEN_HIP_OK; }, // a block reads no further than it writes
@@ -453,22 +528,25 @@ int zen_hip_pcm_hpr_process_host(zen_hip_hpr_t h, const int16_t* in_host, int ch
 }
 
 // ---- offline two-pass engine: ranges of samples with their halos, two outputs and a zeroed residual -----------------------
-int zen_hip_pcm_hpri_process(zen_hip_hpri_t h, const int16_t* audio_host, int channels, size_t n_frames, int16_t* harm, int16_t* perc,
-                             int16_t* resid, int mode, float gain, float peaks[3], size_t range_samples)
+int hpri_host(const char* who, zen_hip_hpri_t h, int in_fmt, const void* audio_host, int channels, size_t n_frames, int out_fmt, void* harm,
+              void* perc, void* resid, int mode, float gain, float peaks[3], size_t range_samples)
 {
 	if (!h)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpri_process: null handle");
-	ZA_TRY(check_mode_channels("pcm_hpri_process", channels, mode));
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: null handle", who);
+	ZA_TRY(check_fmt(who, "input", in_fmt));
+	ZA_TRY(check_fmt(who, "output", out_fmt));
+	ZA_TRY(check_mode_channels(who, channels, mode));
 	const size_t n = n_frames, ch = (size_t)channels;
 	if (n == 0)
 		return ZEN_HIP_OK; // the reference returns three empty vectors
-	if (!audio_host)
-		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpri_process: null argument");
+	const size_t in_sb = (size_t)pcm_sample_bytes(in_fmt), out_sb = (size_t)pcm_sample_bytes(out_fmt);
 	{
-		const Span s[4] = {{(const char*)audio_host, 2 * ch * n}, {(const char*)harm, 2 * n}, {(const char*)perc, 2 * n}, {(const char*)resid, 2 * n}};
+		const Span s[4] = {{(const char*)audio_host, in_sb * ch * n}, {(const char*)harm, out_sb * n}, {(const char*)perc, out_sb * n}, {(const char*)resid, out_sb * n}};
 		if (any_overlap(s, 4))
-			ZA_FAIL(ZEN_HIP_E_BAD_ARG, "pcm_hpri_process: the host buffers must not overlap");
+			ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: the host buffers must not overlap", who);
 	}
+	if (!audio_host)
+		ZA_FAIL(ZEN_HIP_E_BAD_ARG, "%s: null argument", who);
 	size_t a, b; // refusals of the engine (clip too short, a handle of several clips) before anything is touched
 	ZA_ZEN(zen_hip_hpri_range_halo(h, n, 0, n, &a, &b));
 	// ranges: the float path's rule (csrc/hpri.hip: shorter ranges cost more in warm-up halos and small grids than they hide in copies)
@@ -481,10 +559,10 @@ int zen_hip_pcm_hpri_process(zen_hip_hpri_t h, const int16_t* audio_host, int ch
 	std::thread zero_thread;
 	if (resid) {
 		try {
-			zero_thread = std::thread([=] { zero_host(resid, n); });
+			zero_thread = std::thread([=] { zero_host((uint8_t*)resid, n * out_sb); });
 		}
 		catch (...) { // no thread to be had: zeros written here, before the pipeline starts
-			zero_host(resid, n);
+			zero_host((uint8_t*)resid, n * out_sb);
 		}
 	}
 	struct Joiner {
@@ -495,11 +573,11 @@ int zen_hip_pcm_hpri_process(zen_hip_hpri_t h, const int16_t* audio_host, int ch
 				t.join();
 		}
 	} joiner{zero_thread};
-	const Job job = {audio_host, channels, mode, n, range, {harm, perc, nullptr}, gain, peaks};
+	const Job job = {in_fmt, out_fmt, (const uint8_t*)audio_host, channels, mode, n, range, {(uint8_t*)harm, (uint8_t*)perc, nullptr}, gain, peaks};
 	return run_pieces(
 	    h, KIND_HPRI, job, [&](hipStream_t run) { return zen_hip_hpri_set_stream(h, run); },
 	    [&](size_t b, size_t e, size_t* end) { return zen_hip_hpri_range_halo(h, n, b, e, &b, end); }, // a range reads its halo
 	    [&](const float* fin, size_t b, size_t e, float* const out[3]) { return zen_hip_hpri_process_range(h, fin, n, b, e, out[0], out[1]); });
 }
 
-} // extern "C"
+} // namespace
