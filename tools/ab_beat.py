@@ -17,43 +17,15 @@ repeated:
   C  wall time of one hop through zen_hip_beat_run_host, pinned host to pinned host, the same number of calls.
 "condition": one hop completes on the device within its own duration (512 / fs = 11.6 ms) at the MAXIMUM over leg D.
 On the GPU box, under a time limit of its own:  timeout -k 10 600 python tools/ab_beat.py > beat_ab.json"""
-import argparse
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import bench      # noqa: E402  (s_music: the project's test signal)
-import beat_model  # noqa: E402
-import zen_amd    # noqa: E402
-from zen_amd import beat  # noqa: E402
+from _ab import arguments, bench, emit, kernels, per_call, summary, timed, zen_amd
+import beat_model
+from zen_amd import beat
 
 FS, HOP = 44100.0, 512
-
-
-def summary(ts):
-    med = float(np.median(ts))
-    return {"median_ms": med, "min_ms": float(min(ts)), "max_ms": float(max(ts)), "spread_ms": float(max(ts) - min(ts)), "runs": len(ts)}
-
-
-def timed(f):
-    a, b = zen_amd.Event(), zen_amd.Event()
-    a.record()
-    f()
-    b.record()
-    return a.elapsed_ms(b)
-
-
-def kernels(prof, rounds):
-    out = {kn: {"ms_per_round": v["ms"] / rounds, "bytes_per_round": v["bytes"] // rounds, "launches_per_round": v["launches"] // rounds,
-                "GBps": (v["bytes"] / (v["ms"] * 1e-3) / 1e9) if v["ms"] > 0 else None} for kn, v in prof.items()}
-    out["total_ms_per_round"] = sum(v["ms"] for v in prof.values()) / rounds
-    return out
 
 
 def same_bits(a, b):
@@ -79,20 +51,8 @@ def check_tracker(odf, score, flag, tempo):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--seconds", type=float, default=3600.0)
-    ap.add_argument("--batch-seconds", type=float, default=30.0)
-    ap.add_argument("--streams", type=int, default=64)
-    ap.add_argument("--skew", type=int, default=7919)
-    ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--profiled", type=int, default=2)
-    ap.add_argument("--calls", type=int, default=2000)
-    ap.add_argument("--call-warmup", type=int, default=200)
-    ap.add_argument("--check-every", type=int, default=97)
-    ap.add_argument("--model-hops", type=int, default=20000)
-    ap.add_argument("--seed", type=int, default=4242)
-    a = ap.parse_args()
+    a = arguments(seconds=3600.0, batch_seconds=30.0, streams=64, skew=7919, repeats=10, warmup=2, profiled=2, calls=2000, call_warmup=200,
+                  check_every=97, model_hops=20000, seed=4242)
     zen_amd.init(0)
     L = beat.load()
     S = a.streams
@@ -169,9 +129,7 @@ def main():
     for i in range(a.call_warmup + a.calls):
         td.append(timed(lambda: one.run_device(inp.offset(i * HOP), HOP, 1, *outs, out_stride=1)))
         zen_amd.synchronize()
-    td = np.array(td[a.call_warmup:])
-    leg_d = {"calls": int(td.size), "median_ms": float(np.median(td)), "p99_ms": float(np.percentile(td, 99)), "max_ms": float(td.max()),
-             "hop_ms": hop_ms, "max_over_hop": float(td.max() / hop_ms), "within_the_hop_at_the_maximum": bool(td.max() < hop_ms)}
+    leg_d = per_call(td[a.call_warmup:], hop_ms)
     one.reset()
     pin_in, pin_out = zen_amd.PinnedHost(HOP), zen_amd.PinnedHost(4)
     ptr = [pin_out.array.ctypes.data + 4 * k for k in range(4)]
@@ -183,19 +141,17 @@ def main():
         t1 = time.perf_counter()
         assert rc == 0, L.zen_hip_beat_last_error()
         tc.append(1e3 * (t1 - t0))
-    tc = np.array(tc[a.call_warmup:])
-    leg_c = {"calls": int(tc.size), "median_ms": float(np.median(tc)), "p99_ms": float(np.percentile(tc, 99)), "max_ms": float(tc.max()),
-             "hop_ms": hop_ms, "max_over_hop": float(tc.max() / hop_ms)}
+    leg_c = per_call(tc[a.call_warmup:], hop_ms, within=False)
 
-    print(json.dumps({
-        "tool": "tools/ab_beat.py", "device": zen_amd.device_name(), "repeats": a.repeats, "warmup": a.warmup,
+    emit(__file__, {
+        "repeats": a.repeats, "warmup": a.warmup,
         "workload": {"fs": FS, "hop": HOP, "seconds": a.seconds, "batch_seconds": a.batch_seconds, "streams": S, "skew": a.skew, "seed": a.seed,
                      "signal": "one minute of bench.s_music with a click every 0.5 s, repeated"},
         "legs": res, "same_bits_as_the_model": same, "kernels": kern,
         "one_hop_device": leg_d, "one_hop_run_host_wall": leg_c,
         "condition_one_hop_within_its_duration_at_the_maximum": leg_d["within_the_hop_at_the_maximum"],
         "device_bytes": device_bytes,
-    }))
+    })
 
 
 if __name__ == "__main__":

@@ -15,47 +15,16 @@ kernels of this library (slice, fold, overlap, mask, gather, overlap_add) that r
 measures on the same box (tools/ubench_copy.hip).  The transforms and the medians are the engine's kernels and are listed
 with their times only.
 On the GPU box, under a time limit of its own:  timeout -k 10 600 python tools/ab_cqt.py > profiles/cqt_ab.json"""
-import argparse
-import json
-import os
-import sys
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import bench      # noqa: E402  (s_music: the project's test signal; device_copy_bandwidth)
-import zen_amd    # noqa: E402
-from zen_amd import cqt  # noqa: E402
+from _ab import arguments, bench, emit, summary, timed, zen_amd
+from zen_amd import cqt
 
 OWN = ("slice", "fold", "overlap", "mask", "gather", "overlap_add")
 
 
-def summary(ts):
-    return {"median_ms": float(np.median(ts)), "min_ms": float(min(ts)), "max_ms": float(max(ts)), "spread_ms": float(max(ts) - min(ts)),
-            "runs": len(ts)}
-
-
-def timed(f):
-    a, b = zen_amd.Event(), zen_amd.Event()
-    a.record()
-    f()
-    b.record()
-    return a.elapsed_ms(b)
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--seconds", type=float, default=30.0)
-    ap.add_argument("--fs", type=float, default=44100.0)
-    ap.add_argument("--slice", type=int, default=16384)
-    ap.add_argument("--bpo", type=int, default=12)
-    ap.add_argument("--fmin", type=float, default=60.0)
-    ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--profiled", type=int, default=3)
-    ap.add_argument("--seed", type=int, default=4242)
-    a = ap.parse_args()
+    a = arguments(seconds=30.0, fs=44100.0, slice=16384, bpo=12, fmin=60.0, repeats=10, warmup=2, profiled=3, seed=4242)
     zen_amd.init(0)
     n = int(a.seconds * a.fs)
     x = bench.s_music(n, seed=a.seed).astype(np.float32)
@@ -107,13 +76,13 @@ def main():
                                "frac_of_device_copy": gbps / copy_bw if gbps and copy_bw else None})
     kern["total_ms_per_call"] = sum(v["ms"] for v in prof.values()) / a.profiled
 
-    print(json.dumps({
-        "tool": "tools/ab_cqt.py", "device": zen_amd.device_name(), "repeats": a.repeats, "warmup": a.warmup,
+    emit(__file__, {
+        "repeats": a.repeats, "warmup": a.warmup,
         "workload": {"fs": a.fs, "slice": a.slice, "bands_per_octave": a.bpo, "fmin": a.fmin, "seconds": a.seconds, "samples": n, "seed": a.seed,
                      "signal": "bench.s_music", "shape": sh, "coefficient_bytes": 8 * sh["slices"] * sh["bands"] * sh["m"]},
         "legs": res, "kernels_of_S3": kern, "device_copy_GBps": copy_bw, "round_trip_max_abs_error": round_trip,
         "device_bytes": cq.stats()["device_bytes"],
-    }))
+    })
 
 
 if __name__ == "__main__":

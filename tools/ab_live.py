@@ -14,55 +14,19 @@ Workload: one clip of --seconds (600) at 44.1 kHz from a fixed seed, 4096 / 256,
 "condition": a push of hop_h completes within the hop's own duration (hop_h / fs) at the MAXIMUM over leg C's run.
 Also: device_bytes of a session at max_push = hop_h and at 1 s.
 On the GPU box, under a time limit of its own:  timeout -k 10 600 python tools/ab_live.py > live_ab.json"""
-import argparse
 import ctypes as C
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import bench      # noqa: E402  (s_music: the project's test signal; tuned_copy_record: the HBM denominator)
-import zen_amd    # noqa: E402
-from zen_amd import live  # noqa: E402
+from _ab import arguments, bench, class_ms, emit, kernels, per_call, summary, timed, zen_amd
+from zen_amd import live
 
 FS = 44100.0
 
 
-def summary(ts):
-    med = float(np.median(ts))
-    return {"median_ms": med, "min_ms": float(min(ts)), "max_ms": float(max(ts)), "spread_ms": float(max(ts) - min(ts)), "runs": len(ts)}
-
-
-def timed(f):
-    a, b = zen_amd.Event(), zen_amd.Event()
-    a.record()
-    f()
-    b.record()
-    return a.elapsed_ms(b)
-
-
-def class_ms(prof, calls):
-    out = {ps: {k: v["ms"] / calls for k, v in d.items() if v["launches"]} for ps, d in prof.items()}
-    out["total_ms_per_round"] = sum(v for ps in ("pass1", "pass2") for v in out[ps].values())
-    return out
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--seconds", type=float, default=600.0)
-    ap.add_argument("--hop-h", type=int, default=4096)
-    ap.add_argument("--hop-p", type=int, default=256)
-    ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--profiled", type=int, default=2)
-    ap.add_argument("--pushes", type=int, default=2000)
-    ap.add_argument("--push-warmup", type=int, default=200)
-    ap.add_argument("--seed", type=int, default=4242)
-    a = ap.parse_args()
+    a = arguments(seconds=600.0, hop_h=4096, hop_p=256, repeats=10, warmup=2, profiled=2, pushes=2000, push_warmup=200, seed=4242)
     assert a.repeats >= 10 and a.pushes >= 2000 and a.push_warmup >= 200
     copy = bench.tuned_copy_record()        # a process of its own, before this one opens the device
     zen_amd.init(0)
@@ -132,11 +96,7 @@ def main():
         lv.profile(True)
         for _ in range(a.profiled):
             leg_b(name)
-        k = lv.profile_get()
-        kern[name] = {kn: {"ms_per_round": v["ms"] / a.profiled, "bytes_per_round": v["bytes"] // a.profiled,
-                           "launches_per_round": v["launches"] // a.profiled,
-                           "GBps": (v["bytes"] / (v["ms"] * 1e-3) / 1e9) if v["ms"] > 0 else None} for kn, v in k.items()}
-        kern[name]["total_ms_per_round"] = sum(v["ms"] for v in k.values()) / a.profiled
+        kern[name] = kernels(lv.profile_get(), a.profiled)
         eng[name] = class_ms(lv.profile_get_engine(), a.profiled)
         lv.profile(False)
     tuned = max(copy.get("tuned_copy_median_shape_GBps", 0.0), copy.get("tuned_copy_1GiB_GBps", 0.0)) or None
@@ -163,14 +123,11 @@ def main():
             assert rc == 0, L.zen_hip_live_last_error()
             ts.append(1e3 * (t1 - t0))
         assert got.value == hop
-        ts = np.array(ts[a.push_warmup:])
-        leg_c["%d_stream%s" % (S, "s" if S > 1 else "")] = {
-            "pushes": int(ts.size), "median_ms": float(np.median(ts)), "p99_ms": float(np.percentile(ts, 99)), "max_ms": float(ts.max()),
-            "hop_ms": hop_ms, "max_over_hop": float(ts.max() / hop_ms), "within_the_hop_at_the_maximum": bool(ts.max() < hop_ms)}
+        leg_c["%d_stream%s" % (S, "s" if S > 1 else "")] = per_call(ts[a.push_warmup:], hop_ms, "pushes")
         del lv
 
-    print(json.dumps({
-        "tool": "tools/ab_live.py", "device": zen_amd.device_name(), "repeats": a.repeats, "warmup": a.warmup,
+    emit(__file__, {
+        "repeats": a.repeats, "warmup": a.warmup,
         "workload": {"seconds": a.seconds, "samples": n, "hop_h": a.hop_h, "hop_p": a.hop_p, "beta": 2.0, "mask": "hard", "fs": FS,
                      "seed": a.seed, "push_samples": sizes},
         "legs": res, "B_over_A": ratio, "same_samples_as_A": same,
@@ -181,7 +138,7 @@ def main():
         "per_push_wall": leg_c,
         "condition_push_of_hop_h_within_the_hop_at_the_maximum": all(v["within_the_hop_at_the_maximum"] for v in leg_c.values()),
         "device_bytes": device_bytes,
-    }))
+    })
 
 
 if __name__ == "__main__":

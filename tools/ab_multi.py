@@ -15,7 +15,6 @@ in a synchronise.  Before that, in the same run, the two routes' stems are compa
      the split legs read frames made from those rows and write rows of their own, so every leg works on real samples;
      bytes per second next to the box's tuned copy kernel (tools/ubench_copy, bench.py's HBM denominator).
 On the GPU box, under a time limit of its own:  timeout -k 10 600 python tools/ab_multi.py"""
-import argparse
 import json
 import os
 import sys
@@ -23,20 +22,11 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import bench        # noqa: E402  (tuned_copy_record: the box's copy rate)
-import pcm_model    # noqa: E402
-import zen_amd      # noqa: E402
-from zen_amd import multi  # noqa: E402
+from _ab import arguments, bench, ROOT, summary, timed, zen_amd
+import pcm_model
+from zen_amd import multi
 
 FS, HOP_H, HOP_P = 44100.0, 4096, 256
-
-
-def summary(ts):
-    return {"median_ms": float(np.median(ts)), "min_ms": float(min(ts)), "max_ms": float(max(ts)), "spread_ms": float(max(ts) - min(ts)),
-            "runs": len(ts)}
 
 
 def clip(n, channels, seed=0):
@@ -102,11 +92,7 @@ def kernel_leg(n, channels, repeats):
     for r in range(repeats + 1):
         mm.upload(np.array([np.inf, -np.inf], np.float32))
         for k, (f, _) in legs.items():
-            a, b = zen_amd.Event(), zen_amd.Event()
-            a.record()
-            f()
-            b.record()
-            ms = a.elapsed_ms(b)
+            ms = timed(f)
             if r:                        # round 0 warms up
                 times[k].append(ms)
     got = mm.download()
@@ -122,13 +108,7 @@ def kernel_leg(n, channels, repeats):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--seconds", type=float, default=300.0)
-    ap.add_argument("--channels", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--kernel-scale", type=int, default=4)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "multi_ab.json"))
-    a = ap.parse_args()
+    a = arguments(seconds=300.0, channels=2, repeats=5, kernel_scale=4, out=os.path.join(ROOT, "profiles", "multi_ab.json"))
     zen_amd.init(0)
     n = int(a.seconds * FS)
     x16 = clip(n, a.channels)

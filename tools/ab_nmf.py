@@ -19,34 +19,15 @@ copy rate bench.py measures on the same box (tools/ubench_copy.hip) by the bytes
 The host route: the same iteration in numpy (float32 `@`, the BLAS numpy has) for --host-iterations iterations on V copied to
 the host; the seconds for --iterations are those times iterations / host_iterations.
 On the GPU box, under a time limit of its own:  timeout -k 10 600 python tools/ab_nmf.py > profiles/nmf_ab.json"""
-import argparse
-import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import bench      # noqa: E402  (s_music: the project's test signal; device_copy_bandwidth)
-import zen_amd    # noqa: E402
-from zen_amd import nmf  # noqa: E402
+from _ab import arguments, bench, emit, summary, timed, zen_amd
+from zen_amd import nmf
 
 REPSIM_TFLOPS, GUIDE_TFLOPS, PEAK_TFLOPS = 91.9, 122.0, 157.3
-
-
-def summary(ts):
-    return {"median_ms": float(np.median(ts)), "min_ms": float(min(ts)), "max_ms": float(max(ts)), "spread_ms": float(max(ts) - min(ts)),
-            "runs": len(ts)}
-
-
-def timed(f):
-    a, b = zen_amd.Event(), zen_amd.Event()
-    a.record()
-    f()
-    b.record()
-    return a.elapsed_ms(b)
 
 
 def host_iterations(V, W, H, fixed, iterations):
@@ -61,18 +42,7 @@ def host_iterations(V, W, H, fixed, iterations):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--seconds", type=float, default=180.0)
-    ap.add_argument("--fs", type=float, default=44100.0)
-    ap.add_argument("--nfft", type=int, default=2048)
-    ap.add_argument("--components", type=int, default=64)
-    ap.add_argument("--iterations", type=int, default=100)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--profiled", type=int, default=2)
-    ap.add_argument("--host-iterations", type=int, default=5)
-    ap.add_argument("--seed", type=int, default=4242)
-    a = ap.parse_args()
+    a = arguments(seconds=180.0, fs=44100.0, nfft=2048, components=64, iterations=100, repeats=5, warmup=1, profiled=2, host_iterations=5, seed=4242)
     zen_amd.init(0)
     n, H = int(a.seconds * a.fs), a.nfft // 2
     F, m, K = H + 1, nmf.n_frames(n, a.nfft), a.components
@@ -183,12 +153,12 @@ def main():
     host["host_iterations"] = a.host_iterations
     host["threads"] = os.cpu_count() if "OMP_NUM_THREADS" not in os.environ else int(os.environ["OMP_NUM_THREADS"])
 
-    print(json.dumps({
-        "tool": "tools/ab_nmf.py", "device": zen_amd.device_name(), "repeats": a.repeats, "warmup": a.warmup,
+    emit(__file__, {
+        "repeats": a.repeats, "warmup": a.warmup,
         "workload": {"fs": a.fs, "nfft": a.nfft, "seconds": a.seconds, "samples": n, "frames": m, "bins": F, "components": K, "iterations": a.iterations,
                      "seed": a.seed, "signal": "bench.s_music", "product_flop": flop},
         "legs": res, "kernels": kern, "device_copy_GBps": copy_bw, "host_route": host, "device_bytes": sm.stats()["device_bytes"],
-    }))
+    })
 
 
 if __name__ == "__main__":

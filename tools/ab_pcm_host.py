@@ -25,7 +25,6 @@ each kernel's time is below the link's copy time for the piece.  Nothing is asse
   timeout -k 10 900 python tools/ab_pcm_host.py --fmt i24 > pcm24_host_ab.json"""
 import argparse
 import ctypes as C
-import json
 import os
 import subprocess
 import sys
@@ -34,11 +33,8 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import bench      # noqa: E402  (s_music: the project's test signal)
-import zen_amd    # noqa: E402
-from zen_amd import pcm  # noqa: E402
+from _ab import bench, emit, summary, timed, zen_amd
+from zen_amd import pcm
 
 FS, LINK_GBPS = 44100.0, 57.0      # the host link as tools/probe_pcie.cpp measured it, each way
 
@@ -102,11 +98,6 @@ def ms(f):
     return 1e3 * (time.perf_counter() - t0)
 
 
-def summary(ts):
-    return {"median_ms": float(np.median(ts)), "min_ms": float(min(ts)), "max_ms": float(max(ts)), "spread_ms": float(max(ts) - min(ts)),
-            "runs": len(ts)}
-
-
 def kernels_alone_ms(n, n_out):
     """the three new kernels on device-resident data of this shape's size (HIP events, best of 3): their share of a call"""
     x16 = zen_amd.DeviceBuffer(n, np.int16)
@@ -118,11 +109,7 @@ def kernels_alone_ms(n, n_out):
                        ("from_float", lambda: pcm.from_float(f.ptr, n, x16.ptr, mode=pcm.GAIN, gain=1.0))):
         best = 1e30
         for _ in range(4):
-            a, b = zen_amd.Event(), zen_amd.Event()
-            a.record()
-            call()
-            b.record()
-            best = min(best, a.elapsed_ms(b))
+            best = min(best, timed(call))
         out[name] = best
     for b in (x16, f, mm):
         b.free()
@@ -394,13 +381,13 @@ def main():
                 shape, buf, results[-1]["float"]["median_ms"], results[-1]["pcm_gain"]["median_ms"],
                 results[-1]["float_plus_host"]["median_ms"], results[-1]["pcm_peak"]["median_ms"]), file=sys.stderr, flush=True)
     pinned = [r for r in results if r["buffers"] == "pinned"]
-    record = {"tool": "tools/ab_pcm_host.py", "device": zen_amd.device_name(), "pairs": a.pairs, "warmup": a.warmup}
+    record = {"pairs": a.pairs, "warmup": a.warmup}
     if "i16" in fmts:
         record.update({"requirement_met_pinned": bool(pinned and all(r["requirement_gain"] and r["requirement_peak"] for r in pinned)),
                        "results": results})
     if "i24" in fmts:
         record["results_i24"] = results24
-    print(json.dumps(record))
+    emit(__file__, record)
 
 
 if __name__ == "__main__":

@@ -16,58 +16,19 @@ repeated -- a minute is no whole number of chunks, so the chunks differ.
      median, 99th percentile, maximum.
 "condition": one chunk completes within its own duration (4096 / fs = 92.9 ms) at the MAXIMUM over leg C's run.
 On the GPU box, under a time limit of its own:  timeout -k 10 600 python tools/ab_pitch.py > pitch_ab.json"""
-import argparse
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import bench      # noqa: E402  (s_music: the project's test signal; tuned_copy_record: the HBM denominator)
-import pitch_model  # noqa: E402
-import zen_amd    # noqa: E402
-from zen_amd import pitch  # noqa: E402
+from _ab import arguments, bench, emit, kernels, summary, timed, zen_amd
+import pitch_model
+from zen_amd import pitch
 
 FS = 44100.0
 
 
-def summary(ts):
-    med = float(np.median(ts))
-    return {"median_ms": med, "min_ms": float(min(ts)), "max_ms": float(max(ts)), "spread_ms": float(max(ts) - min(ts)), "runs": len(ts)}
-
-
-def timed(f):
-    a, b = zen_amd.Event(), zen_amd.Event()
-    a.record()
-    f()
-    b.record()
-    return a.elapsed_ms(b)
-
-
-def kernels(prof, rounds):
-    out = {kn: {"ms_per_round": v["ms"] / rounds, "bytes_per_round": v["bytes"] // rounds, "launches_per_round": v["launches"] // rounds,
-                "GBps": (v["bytes"] / (v["ms"] * 1e-3) / 1e9) if v["ms"] > 0 else None} for kn, v in prof.items()}
-    out["total_ms_per_round"] = sum(v["ms"] for v in prof.values()) / rounds
-    return out
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--seconds", type=float, default=3600.0)
-    ap.add_argument("--chunk", type=int, default=4096)
-    ap.add_argument("--beta", type=float, default=2.5)
-    ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--profiled", type=int, default=2)
-    ap.add_argument("--calls", type=int, default=2000)
-    ap.add_argument("--call-warmup", type=int, default=200)
-    ap.add_argument("--check-every", type=int, default=97)
-    ap.add_argument("--seed", type=int, default=4242)
-    a = ap.parse_args()
+    a = arguments(seconds=3600.0, chunk=4096, beta=2.5, repeats=10, warmup=2, profiled=2, calls=2000, call_warmup=200, check_every=97, seed=4242)
     assert a.repeats >= 10 and a.calls >= 2000 and a.call_warmup >= 200
     copy = bench.tuned_copy_record()        # a process of its own, before this one opens the device
     zen_amd.init(0)
@@ -156,8 +117,8 @@ def main():
     leg_c = {"calls": int(ts.size), "median_ms": float(np.median(ts)), "p99_ms": float(np.percentile(ts, 99)), "max_ms": float(ts.max()),
              "chunk_ms": chunk_ms, "max_over_chunk": float(ts.max() / chunk_ms), "within_the_chunk_at_the_maximum": bool(ts.max() < chunk_ms)}
 
-    print(json.dumps({
-        "tool": "tools/ab_pitch.py", "device": zen_amd.device_name(), "repeats": a.repeats, "warmup": a.warmup,
+    emit(__file__, {
+        "repeats": a.repeats, "warmup": a.warmup,
         "workload": {"seconds": a.seconds, "chunks": cnt, "chunk": n, "fs": FS, "beta": a.beta, "seed": a.seed,
                      "signal": "one minute of bench.s_music, repeated"},
         "legs": res, "same_bits_as_the_model": same, "share_of_chunks_with_a_pitch": found,
@@ -168,7 +129,7 @@ def main():
         "one_chunk_run_host_wall": leg_c,
         "condition_one_chunk_within_its_duration_at_the_maximum": leg_c["within_the_chunk_at_the_maximum"],
         "device_bytes": device_bytes,
-    }))
+    })
 
 
 if __name__ == "__main__":

@@ -14,18 +14,10 @@ rounds the event times of pack / splice / trim with their bytes and achieved GB/
 (tools/ubench_copy, bench.py's HBM denominator), and the engines' per-class kernel times of B and D.
 "requirement": the better of B and C is faster than A by more than A's spread (max - min).
 On the GPU box, under a time limit of its own:  timeout -k 10 600 python tools/ab_ragged.py > ragged_ab.json"""
-import argparse
-import json
-import os
-import sys
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import bench      # noqa: E402  (s_music: the project's test signal; tuned_copy_record: the HBM denominator)
-import zen_amd    # noqa: E402
-from zen_amd import ragged  # noqa: E402
+from _ab import arguments, bench, class_ms, emit, kernels, timed, zen_amd
+from zen_amd import ragged
 
 FS = 44100.0
 
@@ -37,31 +29,8 @@ def summary(ts, audio_seconds):
             "audio_seconds_per_second_min": audio_seconds / (max(ts) * 1e-3), "audio_seconds_per_second_max": audio_seconds / (min(ts) * 1e-3)}
 
 
-def timed(f):
-    a, b = zen_amd.Event(), zen_amd.Event()
-    a.record()
-    f()
-    b.record()
-    return a.elapsed_ms(b)
-
-
-def class_ms(prof, calls):
-    return {ps: {k: v["ms"] / calls for k, v in d.items() if v["launches"]} for ps, d in prof.items()}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--clips", type=int, default=64)
-    ap.add_argument("--group", type=int, default=16)
-    ap.add_argument("--min-seconds", type=float, default=20.0)
-    ap.add_argument("--max-seconds", type=float, default=40.0)
-    ap.add_argument("--hop-h", type=int, default=4096)
-    ap.add_argument("--hop-p", type=int, default=256)
-    ap.add_argument("--repeats", type=int, default=12)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--profiled", type=int, default=4)
-    ap.add_argument("--seed", type=int, default=20251)
-    a = ap.parse_args()
+    a = arguments(clips=64, group=16, min_seconds=20.0, max_seconds=40.0, hop_h=4096, hop_p=256, repeats=12, warmup=2, profiled=4, seed=20251)
     assert a.repeats >= 10, "at least 10 repeats per leg"
     copy = bench.tuned_copy_record()        # a process of its own, before this one opens the device
     zen_amd.init(0)
@@ -146,15 +115,9 @@ def main():
         leg_d()
     kern = {}
     for name, h in (("B", rg_all), ("C", rg_grp)):
-        k = h.profile_get()
-        kern[name] = {kn: {"ms_per_round": v["ms"] / a.profiled, "bytes_per_round": v["bytes"] // a.profiled,
-                           "launches_per_round": v["launches"] // a.profiled,
-                           "GBps": (v["bytes"] / (v["ms"] * 1e-3) / 1e9) if v["ms"] > 0 else None} for kn, v in k.items()}
-        kern[name]["total_ms_per_round"] = sum(v["ms"] for v in k.values()) / a.profiled
+        kern[name] = kernels(h.profile_get(), a.profiled)
     eng = {"B": class_ms(rg_all.profile_get_engine(), a.profiled), "C": class_ms(rg_grp.profile_get_engine(), a.profiled),
            "D": class_ms(equal.profile_get_all(), a.profiled)}
-    for name in eng:
-        eng[name]["total_ms_per_round"] = sum(v for ps in ("pass1", "pass2") for v in eng[name][ps].values())
     rg_all.profile(False)
     rg_grp.profile(False)
     equal.profile(False)
@@ -164,8 +127,8 @@ def main():
     b_minus_d = res["B"]["median_ms"] - res["D"]["median_ms"]
     engine_diff = eng["B"]["total_ms_per_round"] - eng["D"]["total_ms_per_round"]
     explained = kern["B"]["total_ms_per_round"] + engine_diff
-    print(json.dumps({
-        "tool": "tools/ab_ragged.py", "device": zen_amd.device_name(), "repeats": a.repeats, "warmup": a.warmup,
+    emit(__file__, {
+        "repeats": a.repeats, "warmup": a.warmup,
         "workload": {"clips": C, "group": a.group, "hop_h": a.hop_h, "hop_p": a.hop_p, "beta": 2.0, "mask": "hard", "fs": FS,
                      "seed": a.seed, "min_samples": min(lens), "max_samples": mx, "audio_seconds": audio_seconds,
                      "padded_work_fraction_one_call": sum(lens) / (C * mx), "padded_work_fraction_sorted_groups": fraction,
@@ -183,7 +146,7 @@ def main():
                       "explained_ms": explained, "unexplained_ms": b_minus_d - explained,
                       "spread_ms": max(res["B"]["spread_ms"], res["D"]["spread_ms"]),
                       "accounted_within_spread": bool(abs(b_minus_d - explained) <= max(res["B"]["spread_ms"], res["D"]["spread_ms"]))},
-    }))
+    })
 
 
 if __name__ == "__main__":

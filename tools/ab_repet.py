@@ -14,42 +14,15 @@ test signal (bench.s_music) repeated as the accompaniment, a gliding tone with a
         Cache, so the rate is not an HBM rate; the copy rate it is held against is measured on 1 GiB.
   H     the host route for the same step: V to the host, numpy.median over the repetitions, S back to the device; wall time.
 On the GPU box, under a time limit of its own:  timeout -k 10 600 python tools/ab_repet.py > profiles/repet_ab.json"""
-import argparse
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import bench      # noqa: E402  (s_music: the project's test signal; device_copy_bandwidth)
-import zen_amd    # noqa: E402
-from zen_amd import repet  # noqa: E402
+from _ab import arguments, bench, emit, kernels, summary, timed, zen_amd
+from zen_amd import repet
 
 FS, NFFT = 44100.0, 2048
 HOP, BINS = NFFT // 2, NFFT // 2 + 1
-
-
-def summary(ts):
-    return {"median_ms": float(np.median(ts)), "min_ms": float(min(ts)), "max_ms": float(max(ts)), "spread_ms": float(max(ts) - min(ts)),
-            "runs": len(ts)}
-
-
-def timed(f):
-    a, b = zen_amd.Event(), zen_amd.Event()
-    a.record()
-    f()
-    b.record()
-    return a.elapsed_ms(b)
-
-
-def kernels(prof, rounds):
-    out = {kn: {"ms_per_round": v["ms"] / rounds, "bytes_per_round": v["bytes"] // rounds, "launches_per_round": v["launches"] // rounds,
-                "GBps": (v["bytes"] / (v["ms"] * 1e-3) / 1e9) if v["ms"] > 0 else None} for kn, v in prof.items()}
-    out["total_ms_per_round"] = sum(v["ms"] for v in prof.values()) / rounds
-    return out
 
 
 def clip(seconds, period_frames, seed):
@@ -62,16 +35,7 @@ def clip(seconds, period_frames, seed):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--seconds", type=float, default=180.0)
-    ap.add_argument("--period", type=int, default=86)
-    ap.add_argument("--long-period", type=int, default=258)
-    ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--profiled", type=int, default=2)
-    ap.add_argument("--median-launches", type=int, default=50)
-    ap.add_argument("--seed", type=int, default=4242)
-    a = ap.parse_args()
+    a = arguments(seconds=180.0, period=86, long_period=258, repeats=10, warmup=2, profiled=2, median_launches=50, seed=4242)
     zen_amd.init(0)
     x = clip(a.seconds, a.period, a.seed)
     n = x.size
@@ -141,13 +105,13 @@ def main():
                              # float32 medians of an even count: numpy averages in float32 as well; equal up to that rounding
                              "max_abs_difference_from_numpy_median": float(np.max(np.abs(got - s_host)))}
 
-    print(json.dumps({
-        "tool": "tools/ab_repet.py", "device": zen_amd.device_name(), "repeats": a.repeats, "warmup": a.warmup,
+    emit(__file__, {
+        "repeats": a.repeats, "warmup": a.warmup,
         "workload": {"fs": FS, "nfft": NFFT, "seconds": a.seconds, "samples": n, "frames": m, "bins": BINS, "seed": a.seed,
                      "signal": "%d frames of bench.s_music repeated under a gliding tone" % a.period},
         "legs": res, "kernels": kern, "segment_median_alone": median, "device_copy_GBps": copy_bw,
         "period_found_is_the_true_one": used["F"][0] == a.period, "device_bytes": rp.stats()["device_bytes"],
-    }))
+    })
 
 
 if __name__ == "__main__":

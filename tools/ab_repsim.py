@@ -19,34 +19,15 @@ The host route, once: V copied to the host, S = V V^T over the norms in numpy (f
 and the medians of the first --host-frames frames in numpy (the seconds for all frames are those times m / host_frames), U
 copied back.
 On the GPU box, under a time limit of its own:  timeout -k 10 600 python tools/ab_repsim.py > profiles/repsim_ab.json"""
-import argparse
-import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import bench      # noqa: E402  (s_music: the project's test signal; device_copy_bandwidth)
-import zen_amd    # noqa: E402
-from zen_amd import repsim  # noqa: E402
+from _ab import arguments, bench, emit, summary, timed, zen_amd
+from zen_amd import repsim
 
 GUIDE_TFLOPS, PEAK_TFLOPS = 122.0, 157.3
-
-
-def summary(ts):
-    return {"median_ms": float(np.median(ts)), "min_ms": float(min(ts)), "max_ms": float(max(ts)), "spread_ms": float(max(ts) - min(ts)),
-            "runs": len(ts)}
-
-
-def timed(f):
-    a, b = zen_amd.Event(), zen_amd.Event()
-    a.record()
-    f()
-    b.record()
-    return a.elapsed_ms(b)
 
 
 def host_select(S, dd, k):
@@ -66,16 +47,7 @@ def host_select(S, dd, k):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--seconds", type=float, default=180.0)
-    ap.add_argument("--fs", type=float, default=44100.0)
-    ap.add_argument("--nfft", type=int, default=2048)
-    ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--profiled", type=int, default=3)
-    ap.add_argument("--host-frames", type=int, default=512)
-    ap.add_argument("--seed", type=int, default=4242)
-    a = ap.parse_args()
+    a = arguments(seconds=180.0, fs=44100.0, nfft=2048, repeats=10, warmup=2, profiled=3, host_frames=512, seed=4242)
     zen_amd.init(0)
     n, H = int(a.seconds * a.fs), a.nfft // 2
     bins, m = H + 1, repsim.n_frames(n, a.nfft)
@@ -166,14 +138,14 @@ def main():
                             + (host["select_s_for_host_frames"] + host["median_s_for_host_frames"]) * m / hf)
     host["device_steps_3_to_5_ms"] = sum(kern[s]["ms_per_call"] for s in ("similarity_mfma", "select", "gather_median"))
 
-    print(json.dumps({
-        "tool": "tools/ab_repsim.py", "device": zen_amd.device_name(), "repeats": a.repeats, "warmup": a.warmup,
+    emit(__file__, {
+        "repeats": a.repeats, "warmup": a.warmup,
         "workload": {"fs": a.fs, "nfft": a.nfft, "seconds": a.seconds, "samples": n, "frames": m, "bins": bins, "seed": a.seed, "signal": "bench.s_music",
                      "threshold": repsim.THRESHOLD, "distance_frames": dd, "number": k, "highpass_hz": repsim.HIGHPASS,
                      "mean_frames_per_median": float(counts.mean()), "similarity_flop": flop},
         "legs": res, "kernels_of_W": kern, "device_copy_GBps": copy_bw, "host_route": host,
         "device_bytes": rs.stats()["device_bytes"], "bands_per_call": rs.stats()["bands"] // (a.warmup + a.repeats + a.profiled),
-    }))
+    })
 
 
 if __name__ == "__main__":

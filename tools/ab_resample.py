@@ -17,33 +17,13 @@ how much.
           the separation (libzen_hip), the stretch (libzen_hip_tsm, overlap-add frame 2048 as tools/ab_tsm.py's long leg) and the
           resampler.
 On the GPU box, under a time limit of its own:  timeout -k 10 900 python tools/ab_resample.py > profiles/resample_ab.json"""
-import argparse
-import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import bench      # noqa: E402  (s_music: the project's test signal; device_copy_bandwidth)
-import zen_amd    # noqa: E402
-from zen_amd import resample, tsm  # noqa: E402
-
-
-def summary(ts):
-    return {"median_ms": float(np.median(ts)), "min_ms": float(min(ts)), "max_ms": float(max(ts)), "spread_ms": float(max(ts) - min(ts)),
-            "runs": len(ts)}
-
-
-def timed(f):
-    a, b = zen_amd.Event(), zen_amd.Event()
-    a.record()
-    f()
-    b.record()
-    return a.elapsed_ms(b)
+from _ab import arguments, bench, emit, summary, timed, zen_amd
+from zen_amd import resample, tsm
 
 
 def handle(num, den, quality, poly):
@@ -128,15 +108,7 @@ def shift_leg(x, fs, semitones, a):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batch-seconds", type=float, default=30.0)
-    ap.add_argument("--batch-rows", type=int, default=64)
-    ap.add_argument("--long-seconds", type=float, default=180.0)
-    ap.add_argument("--repeats", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--model-seconds", type=float, default=2.0)
-    ap.add_argument("--seed", type=int, default=4242)
-    a = ap.parse_args()
+    a = arguments(batch_seconds=30.0, batch_rows=64, long_seconds=180.0, repeats=7, warmup=2, model_seconds=2.0, seed=4242)
     zen_amd.init(0)
     copy_bw = bench.device_copy_bandwidth(zen_amd)
     work = []
@@ -162,12 +134,12 @@ def main():
     resample_model.resample(cut, ratios[0][0], ratios[0][1], 16)
     model_s = time.perf_counter() - t0
     device_ms = long["legs"]["%d/%d q16 interp" % ratios[0]]["median_ms"]
-    print(json.dumps({
-        "tool": "tools/ab_resample.py", "device": zen_amd.device_name(), "repeats": a.repeats, "warmup": a.warmup, "seed": a.seed,
+    emit(__file__, {
+        "repeats": a.repeats, "warmup": a.warmup, "seed": a.seed,
         "device_copy_GBps": copy_bw, "tile": resample.TILE, "workloads": work, "shift_hpr": shift_leg(xl, 44100.0, 3, a),
         "host_model": {"seconds_of_audio": a.model_seconds, "wall_s": model_s, "scaled_to_the_long_row_s": model_s * a.long_seconds / a.model_seconds,
                        "over_the_device_call": model_s * a.long_seconds / a.model_seconds / (device_ms * 1e-3)},
-    }))
+    })
 
 
 if __name__ == "__main__":

@@ -15,36 +15,15 @@ Per workload:
   (bench.device_copy_bandwidth), and the walk in microseconds per frame.
   model   the numpy model (tests/tsm_model.py) on the host on the first --model-seconds of the long clip, scaled to its length.
 On the GPU box, under a time limit of its own:  timeout -k 10 900 python tools/ab_tsm.py > profiles/tsm_ab.json"""
-import argparse
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import bench      # noqa: E402  (s_music: the project's test signal; device_copy_bandwidth)
-import zen_amd    # noqa: E402
-from zen_amd import tsm  # noqa: E402
+from _ab import arguments, bench, emit, summary, timed, zen_amd
+from zen_amd import tsm
 
 FS = 44100.0
 BANDWIDTH_SHAPED = ("frame", "analysis", "peaks", "spectrum", "overlap_add")
-
-
-def summary(ts):
-    return {"median_ms": float(np.median(ts)), "min_ms": float(min(ts)), "max_ms": float(max(ts)), "spread_ms": float(max(ts) - min(ts)),
-            "runs": len(ts)}
-
-
-def timed(f):
-    a, b = zen_amd.Event(), zen_amd.Event()
-    a.record()
-    f()
-    b.record()
-    return a.elapsed_ms(b)
 
 
 def stems(n, clips, seed):
@@ -98,17 +77,7 @@ def workload(name, seconds, clips, nfft, nfft_ola, alpha, a, copy_bw):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--alpha", type=float, default=1.5)
-    ap.add_argument("--long-seconds", type=float, default=180.0)
-    ap.add_argument("--batch-seconds", type=float, default=30.0)
-    ap.add_argument("--batch-clips", type=int, default=64)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--profiled", type=int, default=2)
-    ap.add_argument("--model-seconds", type=float, default=2.0)
-    ap.add_argument("--seed", type=int, default=4242)
-    a = ap.parse_args()
+    a = arguments(alpha=1.5, long_seconds=180.0, batch_seconds=30.0, batch_clips=64, repeats=5, warmup=1, profiled=2, model_seconds=2.0, seed=4242)
     zen_amd.init(0)
     copy_bw = bench.device_copy_bandwidth(zen_amd)
     long, x = workload("long", a.long_seconds, 1, 4096, 2048, a.alpha, a, copy_bw)
@@ -118,12 +87,12 @@ def main():
     t0 = time.perf_counter()
     tsm_model.stretch_hp(cut, cut, 4096, 2048, a.alpha, cut)
     model_s = time.perf_counter() - t0
-    print(json.dumps({
-        "tool": "tools/ab_tsm.py", "device": zen_amd.device_name(), "repeats": a.repeats, "warmup": a.warmup, "fs": FS, "seed": a.seed,
+    emit(__file__, {
+        "repeats": a.repeats, "warmup": a.warmup, "fs": FS, "seed": a.seed,
         "device_copy_GBps": copy_bw, "workloads": [long, batch],
         "host_model": {"seconds_of_audio": a.model_seconds, "wall_s": model_s, "scaled_to_the_long_clip_s": model_s * a.long_seconds / a.model_seconds,
                        "over_the_device_call": model_s * a.long_seconds / a.model_seconds / (long["legs"]["hp"]["median_ms"] * 1e-3)},
-    }))
+    })
 
 
 if __name__ == "__main__":

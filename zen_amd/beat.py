@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _addon
+from ._addon import _f, _i, _pd, _pull, _sz, _vp
 from . import lib as _zl
 
 KERNELS = ("frame", "fft", "csd", "track")
@@ -24,8 +25,6 @@ class Stats(C.Structure):
 
 
 # every symbol zen_amd/beat/zen_hip_beat.h declares: (name, restype, argtypes)
-_vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
-_pd, _pull = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
 SYMBOLS = [
     ("zen_hip_beat_last_error", C.c_char_p, []),
     ("zen_hip_beat_version", C.c_char_p, []),
@@ -41,19 +40,8 @@ SYMBOLS = [
     ("zen_hip_beat_table", _i, [_f, _sz, _i, _sz, _vp, _sz]),
 ]
 
-
-def load():
-    """Load libzen_hip_beat.so, building it first where it is absent (_addon.load).  Raises if that fails."""
-    return _addon.load("beat", SYMBOLS)
-
-
-def _ck(rc):
-    _addon.check(rc, load().zen_hip_beat_last_error)
-
-
-def _ptr(b):
-    """a DeviceBuffer, a raw device address or None"""
-    return getattr(b, "ptr", b)
+_lib = _addon.Library("beat", SYMBOLS, kernels=KERNELS, stats=Stats)
+load, _ck, _ptr = _lib.load, _lib.check, _addon.ptr
 
 
 def table(fs, hop, which, index=0):
@@ -71,34 +59,20 @@ def beat_times(beat, hop, fs):
     return np.flatnonzero(np.asarray(beat) > 0) * hop / float(fs)
 
 
-class Beat:
+class Beat(_addon.Handle):
     """zen_hip_beat_t: hops of `hop` samples of n_streams rows per call; the state carries over from call to call."""
+    _lib = _lib
 
     def __init__(self, fs, hop=512, n_streams=1, max_hops=0):
-        h = C.c_void_p()
-        _ck(load().zen_hip_beat_create(fs, hop, n_streams, max_hops, C.byref(h)))
-        self._h = h.value
+        self._create(fs, hop, n_streams, max_hops)
         self.fs, self.hop, self.n_streams = fs, hop, n_streams
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            load().zen_hip_beat_destroy(self._h)
-            self._h = None
-
-    def set_stream(self, stream):
-        _ck(load().zen_hip_beat_set_stream(self._h, stream))
-
     def reset(self):
-        _ck(load().zen_hip_beat_reset(self._h))
-
-    def stats(self):
-        st = Stats()
-        _ck(load().zen_hip_beat_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in Stats._fields_}
+        _ck(self._L.zen_hip_beat_reset(self._h))
 
     def run_device(self, in_dev, in_stride, n_hops, odf=None, score=None, beat=None, tempo=None, out_stride=0):
         """DeviceBuffers or device addresses (ints, e.g. DeviceBuffer.offset(k)).  Asynchronous on the handle's stream."""
-        _ck(load().zen_hip_beat_run_device(self._h, _ptr(in_dev), in_stride, n_hops, _ptr(odf), _ptr(score), _ptr(beat), _ptr(tempo), out_stride))
+        _ck(self._L.zen_hip_beat_run_device(self._h, _ptr(in_dev), in_stride, n_hops, _ptr(odf), _ptr(score), _ptr(beat), _ptr(tempo), out_stride))
 
     def run(self, x):
         """x: float32, (m,) for one stream or (n_streams, m); every whole hop of it.  Returns (odf, score, beat, tempo), each
@@ -109,15 +83,8 @@ class Beat:
         m = x.shape[1]
         cnt = m // self.hop
         outs = [np.empty((self.n_streams, cnt), np.float32) for _ in range(4)]
-        _ck(load().zen_hip_beat_run_host(self._h, x.ctypes.data if cnt else None, m, cnt, *(o.ctypes.data if cnt else None for o in outs), cnt))
+        _ck(self._L.zen_hip_beat_run_host(self._h, x.ctypes.data if cnt else None, m, cnt, *(o.ctypes.data if cnt else None for o in outs), cnt))
         return tuple(r[0] if one else r for r in outs)
-
-    def profile(self, enable=True):
-        _ck(load().zen_hip_beat_profile(self._h, int(bool(enable))))
-
-    def profile_get(self):
-        """{"frame" | "fft" | "csd" | "track": {"ms", "bytes", "launches"}} since the last call; synchronises."""
-        return _addon.profile_get(_ck, load().zen_hip_beat_profile_get, self._h, KERNELS)
 
 
 class HprTracker:

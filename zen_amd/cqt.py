@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _addon
+from ._addon import _d, _f, _i, _pd, _psz, _pull, _sz, _vp
 from . import lib as _zl
 
 KERNELS = ("slice", "slice_fft", "fold", "band_ifft", "overlap", "median_time", "median_freq", "mask", "band_fft", "gather", "slice_ifft",
@@ -29,8 +30,6 @@ class Shape(C.Structure):
 
 
 # every symbol zen_amd/cqt/zen_hip_cqt.h declares: (name, restype, argtypes)
-_vp, _sz, _i, _f, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double
-_pd, _pull, _psz = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong), C.POINTER(C.c_size_t)
 SYMBOLS = [
     ("zen_hip_cqt_last_error", C.c_char_p, []),
     ("zen_hip_cqt_version", C.c_char_p, []),
@@ -51,19 +50,8 @@ SYMBOLS = [
     ("zen_hip_cqt_profile_get", _i, [_vp, _pd, _pull, _pull]),
 ]
 
-
-def load():
-    """Load libzen_hip_cqt.so, building it first where it is absent (_addon.load).  Raises if that fails."""
-    return _addon.load("cqt", SYMBOLS)
-
-
-def _ck(rc):
-    _addon.check(rc, load().zen_hip_cqt_last_error, zg_codes=(1,))      # ZEN_HIP_E_FILTER_TOO_BIG is the reference's exception
-
-
-def _ptr(b):
-    """a DeviceBuffer, a raw device address or None"""
-    return getattr(b, "ptr", b)
+_lib = _addon.Library("cqt", SYMBOLS, (1,), KERNELS, Stats)
+load, _ck, _ptr = _lib.load, _lib.check, _addon.ptr      # code 1, ZEN_HIP_E_FILTER_TOO_BIG, is the reference's exception
 
 
 def plan(fs, slice_len, bands_per_octave, fmin):
@@ -82,61 +70,45 @@ def table(fs, slice_len, bands_per_octave, fmin, which):
     return out
 
 
-class Cqt:
+class Cqt(_addon.Handle):
     """zen_hip_cqt_t: n_clips clips of exactly n_samples samples per call"""
+    _lib = _lib
 
     def __init__(self, fs, slice_len=16384, bands_per_octave=12, fmin=60.0, n_clips=1, n_samples=1 << 20, beta=0.0, soft=False, lh=0, lp=0):
-        h = C.c_void_p()
-        _ck(load().zen_hip_cqt_create(fs, slice_len, bands_per_octave, fmin, n_clips, n_samples, C.byref(h)))
-        self._h = h.value
+        self._create(fs, slice_len, bands_per_octave, fmin, n_clips, n_samples)
         self.fs, self.slice_len, self.n_clips, self.n_samples = fs, slice_len, n_clips, n_samples
         if beta or soft or lh or lp:
             self.set_params(beta, soft, lh, lp)
         sh = self.shape()
         self.n_slices, self.n_bands, self.m, self.columns = sh["slices"], sh["bands"], sh["m"], sh["columns"]
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            load().zen_hip_cqt_destroy(self._h)
-            self._h = None
-
-    def set_stream(self, stream):
-        _ck(load().zen_hip_cqt_set_stream(self._h, stream))
-
     def set_params(self, beta=0.0, soft=False, lh=0, lp=0):
         """0 stands for the default: beta 2, 0.2 s of columns, one octave of bands"""
-        _ck(load().zen_hip_cqt_set_params(self._h, beta, int(bool(soft)), lh, lp))
+        _ck(self._L.zen_hip_cqt_set_params(self._h, beta, int(bool(soft)), lh, lp))
 
     def shape(self):
         sh = Shape()
-        _ck(load().zen_hip_cqt_shape(self._h, C.byref(sh)))
-        return {k: getattr(sh, k) for k, _ in Shape._fields_}
-
-    def stats(self):
-        st = Stats()
-        _ck(load().zen_hip_cqt_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in Stats._fields_}
+        _ck(self._L.zen_hip_cqt_shape(self._h, C.byref(sh)))
+        return _addon.as_dict(sh)
 
     # ---- device memory: DeviceBuffers or device addresses; asynchronous on the handle's stream
     def forward_device(self, in_dev, in_stride, coef_dev):
-        _ck(load().zen_hip_cqt_forward_device(self._h, _ptr(in_dev), in_stride, _ptr(coef_dev)))
+        _ck(self._L.zen_hip_cqt_forward_device(self._h, _ptr(in_dev), in_stride, _ptr(coef_dev)))
 
     def spectrogram_device(self, in_dev, in_stride, v_dev, v_stride):
-        _ck(load().zen_hip_cqt_spectrogram_device(self._h, _ptr(in_dev), in_stride, _ptr(v_dev), v_stride))
+        _ck(self._L.zen_hip_cqt_spectrogram_device(self._h, _ptr(in_dev), in_stride, _ptr(v_dev), v_stride))
 
     def inverse_device(self, coef_dev, out_dev, out_stride):
-        _ck(load().zen_hip_cqt_inverse_device(self._h, _ptr(coef_dev), _ptr(out_dev), out_stride))
+        _ck(self._L.zen_hip_cqt_inverse_device(self._h, _ptr(coef_dev), _ptr(out_dev), out_stride))
 
     def separate_device(self, in_dev, in_stride, harmonic=None, percussive=None, residual=None, out_stride=0):
-        _ck(load().zen_hip_cqt_separate_device(self._h, _ptr(in_dev), in_stride, _ptr(harmonic), _ptr(percussive), _ptr(residual), out_stride))
+        _ck(self._L.zen_hip_cqt_separate_device(self._h, _ptr(in_dev), in_stride, _ptr(harmonic), _ptr(percussive), _ptr(residual), out_stride))
 
     # ---- host arrays; synchronous
     def _clips(self, x):
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        one = x.ndim == 1
-        x = x.reshape(self.n_clips, -1)
+        x, one = _addon.clips(x, self.n_clips)
         assert x.shape[1] == self.n_samples, "the session takes clips of %d samples" % self.n_samples
-        return x, (lambda a: None if a is None else a[0]) if one else (lambda a: a)
+        return x, _addon.pick(one)
 
     def forward(self, x):
         """x: float32, (n,) for one clip or (n_clips, n).  The coefficients, (ns, nb, M) or (n_clips, ns, nb, M) complex64."""
@@ -172,16 +144,9 @@ class Cqt:
         """(harmonic, percussive, residual) of x, (n,) or (n_clips, n) float32; a stem that was not asked for is None"""
         x, pick = self._clips(x)
         out = [np.empty_like(x) if w else None for w in (harmonic, percussive, residual)]
-        _ck(load().zen_hip_cqt_separate_host(self._h, x.ctypes.data, self.n_samples, *(None if o is None else o.ctypes.data for o in out),
-                                             self.n_samples))
+        _ck(self._L.zen_hip_cqt_separate_host(self._h, x.ctypes.data, self.n_samples, *(None if o is None else o.ctypes.data for o in out),
+                                              self.n_samples))
         return tuple(pick(o) for o in out)
-
-    def profile(self, enable=True):
-        _ck(load().zen_hip_cqt_profile(self._h, int(bool(enable))))
-
-    def profile_get(self):
-        """{kernel: {"ms", "bytes", "launches"}} since the last call; synchronises."""
-        return _addon.profile_get(_ck, load().zen_hip_cqt_profile_get, self._h, KERNELS)
 
 
 def separate(x, fs, slice_len=16384, bands_per_octave=12, fmin=60.0, beta=0.0, soft=False):

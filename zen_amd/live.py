@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _addon
+from ._addon import _f, _i, _pd, _psz, _pull, _sz, _vp
 from . import lib as _zl
 
 KERNELS = ("feed", "mid", "out")
@@ -22,8 +23,6 @@ class Stats(C.Structure):
 
 
 # every symbol zen_amd/live/zen_hip_live.h declares: (name, restype, argtypes)
-_vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
-_psz, _pd, _pull = C.POINTER(C.c_size_t), C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
 SYMBOLS = [
     ("zen_hip_live_last_error", C.c_char_p, []),
     ("zen_hip_live_version", C.c_char_p, []),
@@ -47,13 +46,8 @@ SYMBOLS = [
     ("zen_hip_live_profile_get_engine", _i, [_vp, _i, _pd, _pull]),
 ]
 
-def load():
-    """Load libzen_hip_live.so, building it first where it is absent (_addon.load).  Raises if that fails."""
-    return _addon.load("live", SYMBOLS)
-
-
-def _ck(rc):
-    _addon.check(rc, load().zen_hip_live_last_error, (_zl.E_HOPS_NOT_DIVISIBLE,))
+_lib = _addon.Library("live", SYMBOLS, (_zl.E_HOPS_NOT_DIVISIBLE,), KERNELS, Stats)
+load, _ck = _lib.load, _lib.check
 
 
 def max_samples(hop_h, hop_p):
@@ -63,60 +57,46 @@ def max_samples(hop_h, hop_p):
     return out.value
 
 
-class Live:
+class Live(_addon.Handle, _addon.EngineProfiled):
     """zen_hip_live_t: one session of n_streams streams in lock step."""
+    _lib = _lib
 
     def __init__(self, fs, hop_h=4096, hop_p=256, beta_h=2.0, beta_p=2.0, nocopybord=False, n_streams=1, max_push=0):
-        h = C.c_void_p()
-        _ck(load().zen_hip_live_create(fs, hop_h, hop_p, beta_h, beta_p, int(nocopybord), n_streams, max_push, C.byref(h)))
-        self._h = h.value
+        self._create(fs, hop_h, hop_p, beta_h, beta_p, int(nocopybord), n_streams, max_push)
         self.n_streams, self.hop_h, self.hop_p = n_streams, hop_h, hop_p
         n = C.c_size_t()
-        _ck(load().zen_hip_live_latency(self._h, C.byref(n)))
+        _ck(self._L.zen_hip_live_latency(self._h, C.byref(n)))
         self.latency = n.value
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            load().zen_hip_live_destroy(self._h)
-            self._h = None
-
     def use_sse_filter(self):
-        _ck(load().zen_hip_live_use_sse_filter(self._h))
+        _ck(self._L.zen_hip_live_use_sse_filter(self._h))
 
     def use_soft_mask(self):
-        _ck(load().zen_hip_live_use_soft_mask(self._h))
-
-    def set_stream(self, stream):
-        _ck(load().zen_hip_live_set_stream(self._h, stream))
+        _ck(self._L.zen_hip_live_use_soft_mask(self._h))
 
     def reset(self):
-        _ck(load().zen_hip_live_reset(self._h))
+        _ck(self._L.zen_hip_live_reset(self._h))
 
     def produces(self, m):
         n = C.c_size_t()
-        _ck(load().zen_hip_live_produces(self._h, m, C.byref(n)))
+        _ck(self._L.zen_hip_live_produces(self._h, m, C.byref(n)))
         return n.value
 
     def pending(self):
         n = C.c_size_t()
-        _ck(load().zen_hip_live_pending(self._h, C.byref(n)))
+        _ck(self._L.zen_hip_live_pending(self._h, C.byref(n)))
         return n.value
-
-    def stats(self):
-        st = Stats()
-        _ck(load().zen_hip_live_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in Stats._fields_}
 
     def push_device(self, in_dev, m, in_stride, harm=None, perc=None, dry=None, out_stride=0):
         """Device pointers (ints, e.g. DeviceBuffer.ptr).  Asynchronous on the handle's stream; returns the samples written to
         each output row."""
         n = C.c_size_t()
-        _ck(load().zen_hip_live_push_device(self._h, in_dev, m, in_stride, harm, perc, dry, out_stride, C.byref(n)))
+        _ck(self._L.zen_hip_live_push_device(self._h, in_dev, m, in_stride, harm, perc, dry, out_stride, C.byref(n)))
         return n.value
 
     def finish_device(self, harm=None, perc=None, dry=None, out_stride=0):
         n = C.c_size_t()
-        _ck(load().zen_hip_live_finish_device(self._h, harm, perc, dry, out_stride, C.byref(n)))
+        _ck(self._L.zen_hip_live_finish_device(self._h, harm, perc, dry, out_stride, C.byref(n)))
         return n.value
 
     def _outs(self, cnt, want):
@@ -131,8 +111,8 @@ class Live:
         cnt = self.produces(m)
         outs = self._outs(cnt, want)
         n = C.c_size_t()
-        _ck(load().zen_hip_live_push_host(self._h, x.ctypes.data if m else None, m, m, *(o.ctypes.data if o is not None and cnt else None
-                                                                                          for o in outs), cnt, C.byref(n)))
+        _ck(self._L.zen_hip_live_push_host(self._h, x.ctypes.data if m else None, m, m, *(o.ctypes.data if o is not None and cnt else None
+                                                                                           for o in outs), cnt, C.byref(n)))
         assert n.value == cnt
         return tuple(outs)
 
@@ -141,17 +121,6 @@ class Live:
         cnt = self.pending()
         outs = self._outs(cnt, want)
         n = C.c_size_t()
-        _ck(load().zen_hip_live_finish_host(self._h, *(o.ctypes.data if o is not None and cnt else None for o in outs), cnt, C.byref(n)))
+        _ck(self._L.zen_hip_live_finish_host(self._h, *(o.ctypes.data if o is not None and cnt else None for o in outs), cnt, C.byref(n)))
         assert n.value == cnt
         return tuple(outs)
-
-    def profile(self, enable=True):
-        _ck(load().zen_hip_live_profile(self._h, int(bool(enable))))
-
-    def profile_get(self):
-        """{"feed" | "mid" | "out": {"ms", "bytes", "launches"}} since the last call; synchronises."""
-        return _addon.profile_get(_ck, load().zen_hip_live_profile_get, self._h, KERNELS)
-
-    def profile_get_engine(self):
-        """The engines' per-class kernel times, as HPRIOffline.profile_get_all."""
-        return _addon.profile_get_engine(_ck, load().zen_hip_live_profile_get_engine, self._h)

@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _addon
+from ._addon import _f, _i, _sz, _vp
 from . import lib as _zl
 
 I16, F32 = 0, 1
@@ -23,7 +24,7 @@ class Stats(C.Structure):
 
 
 # every symbol zen_amd/multi/zen_hip_multi.h declares: (name, restype, argtypes)
-_vp, _sz, _i, _f, _u = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_uint
+_u = C.c_uint
 SYMBOLS = [
     ("zen_hip_multi_last_error", C.c_char_p, []),
     ("zen_hip_multi_version", C.c_char_p, []),
@@ -48,19 +49,8 @@ SYMBOLS = [
     ("zen_hip_multi_realtime_host", _i, [_vp, _i, _vp, _sz, _vp, _vp, _vp, _f]),
 ]
 
-
-def load():
-    """Load libzen_hip_multi.so, building it first where it is absent (_addon.load).  Raises if that fails."""
-    return _addon.load("multi", SYMBOLS)
-
-
-def _ck(rc):
-    _addon.check(rc, load().zen_hip_multi_last_error)
-
-
-def _ptr(b):
-    """a DeviceBuffer, a raw device address or None"""
-    return getattr(b, "ptr", b)
+_lib = _addon.Library("multi", SYMBOLS)
+load, _ck, _ptr = _lib.load, _lib.check, _addon.ptr
 
 
 def _fmt(dtype):
@@ -96,38 +86,29 @@ def join(fmt, rows_dev, channels, n_frames, row_stride, dst_dev, mode=GAIN, gain
     _ck(load().zen_hip_multi_join(fmt, _ptr(rows_dev), channels, n_frames, row_stride, mode, gain, _ptr(minmax_dev), _ptr(dst_dev), stream))
 
 
-class Offline:
+class Offline(_addon.Owner):
     """zen_hip_multi_offline_t: the two-pass separation of every channel of an interleaved clip."""
+    _lib, _prefix = _lib, "offline_"
 
     def __init__(self, fs, hop_h=4096, hop_p=256, beta_h=2.0, beta_p=2.0, nocopybord=False, channels=2):
-        h = C.c_void_p()
-        _ck(load().zen_hip_multi_offline_create(fs, hop_h, hop_p, beta_h, beta_p, int(nocopybord), channels, C.byref(h)))
-        self._h = h.value
+        self._create(fs, hop_h, hop_p, beta_h, beta_p, int(nocopybord), channels)
         self.channels = channels
         self.peaks = None
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            load().zen_hip_multi_offline_destroy(self._h)
-            self._h = None
-
     def use_sse_filter(self):
-        _ck(load().zen_hip_multi_offline_use_sse_filter(self._h))
+        _ck(self._L.zen_hip_multi_offline_use_sse_filter(self._h))
 
     def use_soft_mask(self):
-        _ck(load().zen_hip_multi_offline_use_soft_mask(self._h))
-
-    def set_stream(self, stream):
-        _ck(load().zen_hip_multi_offline_set_stream(self._h, stream))
+        _ck(self._L.zen_hip_multi_offline_use_soft_mask(self._h))
 
     def stats(self):
         st = Stats()
-        _ck(load().zen_hip_multi_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in Stats._fields_}
+        _ck(self._L.zen_hip_multi_stats(self._h, C.byref(st)))
+        return _addon.as_dict(st)
 
     def process_device(self, fmt, in_dev, n_frames, harm=None, perc=None, mode=PEAK, gain=32767.0, peaks_dev=None):
         """DeviceBuffers or device addresses of interleaved frames.  Asynchronous on the handle's stream."""
-        _ck(load().zen_hip_multi_offline_device(self._h, fmt, _ptr(in_dev), n_frames, _ptr(harm), _ptr(perc), mode, gain, _ptr(peaks_dev)))
+        _ck(self._L.zen_hip_multi_offline_device(self._h, fmt, _ptr(in_dev), n_frames, _ptr(harm), _ptr(perc), mode, gain, _ptr(peaks_dev)))
 
     def process(self, x, mode=PEAK, gain=32767.0, want=("harm", "perc")):
         """x: [n_frames, channels], int16 or float32.  Returns {"harm": ..., "perc": ...} of x's shape and dtype (only the
@@ -136,44 +117,34 @@ class Offline:
         outs = {k: np.empty_like(x) for k in ("harm", "perc") if k in want}
         pk = np.zeros(2, np.float32)
         p = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        _ck(load().zen_hip_multi_offline_host(self._h, fmt, p(x), x.shape[0], p(outs.get("harm")), p(outs.get("perc")), mode, gain,
-                                              pk.ctypes.data))
+        _ck(self._L.zen_hip_multi_offline_host(self._h, fmt, p(x), x.shape[0], p(outs.get("harm")), p(outs.get("perc")), mode, gain,
+                                               pk.ctypes.data))
         self.peaks = pk
         return outs
 
 
-class Realtime:
+class Realtime(_addon.Owner):
     """zen_hip_multi_realtime_t: the causal separation of every channel, block by block; the state carries over."""
-
+    _lib, _prefix = _lib, "realtime_"
     NAMES = (("harm", _zl.OUTPUT_HARMONIC), ("perc", _zl.OUTPUT_PERCUSSIVE), ("resid", _zl.OUTPUT_RESIDUAL))
 
     def __init__(self, fs, hop=256, beta=2.0, output_flags=_zl.OUTPUT_HARMONIC | _zl.OUTPUT_PERCUSSIVE | _zl.OUTPUT_RESIDUAL, channels=2,
                  max_hops=0):
-        h = C.c_void_p()
-        _ck(load().zen_hip_multi_realtime_create(fs, hop, beta, output_flags, channels, max_hops, C.byref(h)))
-        self._h = h.value
+        self._create(fs, hop, beta, output_flags, channels, max_hops)
         self.hop, self.channels, self.flags = hop, channels, output_flags
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            load().zen_hip_multi_realtime_destroy(self._h)
-            self._h = None
-
     def use_sse_filter(self):
-        _ck(load().zen_hip_multi_realtime_use_sse_filter(self._h))
+        _ck(self._L.zen_hip_multi_realtime_use_sse_filter(self._h))
 
     def use_soft_mask(self):
-        _ck(load().zen_hip_multi_realtime_use_soft_mask(self._h))
+        _ck(self._L.zen_hip_multi_realtime_use_soft_mask(self._h))
 
     def reset(self):
-        _ck(load().zen_hip_multi_realtime_reset(self._h))
-
-    def set_stream(self, stream):
-        _ck(load().zen_hip_multi_realtime_set_stream(self._h, stream))
+        _ck(self._L.zen_hip_multi_realtime_reset(self._h))
 
     def process_device(self, fmt, in_dev, n_hops, harm=None, perc=None, resid=None, gain=32767.0):
         """DeviceBuffers or device addresses of interleaved frames.  Asynchronous on the handle's stream."""
-        _ck(load().zen_hip_multi_realtime_device(self._h, fmt, _ptr(in_dev), n_hops, _ptr(harm), _ptr(perc), _ptr(resid), gain))
+        _ck(self._L.zen_hip_multi_realtime_device(self._h, fmt, _ptr(in_dev), n_hops, _ptr(harm), _ptr(perc), _ptr(resid), gain))
 
     def process(self, x, gain=32767.0):
         """x: [n_hops * hop, channels], int16 or float32 (whole hops).  Returns {"harm", "perc", "resid"} (those of the
@@ -183,6 +154,6 @@ class Realtime:
             raise ValueError("%d frames are not whole hops of %d" % (x.shape[0], self.hop))
         outs = {k: np.empty_like(x) for k, bit in self.NAMES if self.flags & bit}
         p = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
-        _ck(load().zen_hip_multi_realtime_host(self._h, fmt, p(x), x.shape[0] // self.hop, p(outs.get("harm")), p(outs.get("perc")),
-                                               p(outs.get("resid")), gain))
+        _ck(self._L.zen_hip_multi_realtime_host(self._h, fmt, p(x), x.shape[0] // self.hop, p(outs.get("harm")), p(outs.get("perc")),
+                                                p(outs.get("resid")), gain))
         return outs

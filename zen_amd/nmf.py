@@ -14,6 +14,7 @@ import struct
 import numpy as np
 
 from . import _addon
+from ._addon import _f, _i, _pd, _pull, _sz, _vp
 
 KERNELS = ("frame", "fft", "magnitude", "ratio_mfma", "ratio_valu", "update_h_mfma", "update_h_valu", "update_w_mfma", "update_w_valu", "mask",
            "ifft", "overlap_add")
@@ -30,8 +31,6 @@ class Stats(C.Structure):
 
 
 # every symbol zen_amd/nmf/zen_hip_nmf.h declares: (name, restype, argtypes)
-_vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
-_pd, _pull = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
 _process = [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _i, _vp, _sz, _vp, _sz]
 SYMBOLS = [
     ("zen_hip_nmf_last_error", C.c_char_p, []),
@@ -51,36 +50,15 @@ SYMBOLS = [
     ("zen_hip_nmf_table", _i, [_sz, _i, _vp, _sz]),
 ]
 
-
-def load():
-    """Load libzen_hip_nmf.so, building it first where it is absent (_addon.load).  Raises if that fails."""
-    return _addon.load("nmf", SYMBOLS)
-
-
-def _ck(rc):
-    _addon.check(rc, load().zen_hip_nmf_last_error)
-
-
-def _ptr(b):
-    """a DeviceBuffer, a raw device address or None"""
-    return getattr(b, "ptr", b)
-
-
-def n_frames(n, nfft):
-    return -(-n // (nfft // 2)) + 1
+_lib = _addon.Library("nmf", SYMBOLS, kernels=KERNELS, stats=Stats)
+load, _ck, _ptr = _lib.load, _lib.check, _addon.ptr
+n_frames, table = _addon.n_frames, _lib.stft_table
 
 
 def init(seed, count):
     """`count` initial values in (0, 1] from `seed` (splitmix64) as a float32 array; needs no device"""
     out = np.empty(count, np.float32)
     _ck(load().zen_hip_nmf_init(seed & 0xFFFFFFFFFFFFFFFF, out.size, out.ctypes.data))
-    return out
-
-
-def table(nfft, which):
-    """the window (nfft values) or the overlap divisor (nfft / 2 values) as a float32 array; needs no device"""
-    out = np.empty(nfft if which == TABLE_WINDOW else nfft // 2, np.float32)
-    _ck(load().zen_hip_nmf_table(nfft, which, out.ctypes.data, out.size))
     return out
 
 
@@ -104,45 +82,29 @@ def update_w_device(h_dev, h_stride, q_dev, q_stride, w_dev, w_stride, component
                                            _ptr(out_dev), out_stride, route, stream))
 
 
-class Nmf:
+class Nmf(_addon.Handle):
     """zen_hip_nmf_t: n_clips clips of up to max_samples samples per call, each factorised on its own with `components`
     components"""
+    _lib = _lib
 
     def __init__(self, fs, nfft=2048, components=32, n_clips=1, max_samples=1 << 20):
-        h = C.c_void_p()
-        _ck(load().zen_hip_nmf_create(fs, nfft, components, n_clips, max_samples, C.byref(h)))
-        self._h = h.value
+        self._create(fs, nfft, components, n_clips, max_samples)
         self.fs, self.nfft, self.hop, self.bins = fs, nfft, nfft // 2, nfft // 2 + 1
         self.components, self.n_clips, self.max_samples = components, n_clips, max_samples
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            load().zen_hip_nmf_destroy(self._h)
-            self._h = None
-
-    def set_stream(self, stream):
-        _ck(load().zen_hip_nmf_set_stream(self._h, stream))
-
-    def stats(self):
-        st = Stats()
-        _ck(load().zen_hip_nmf_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in Stats._fields_}
 
     def process_device(self, in_dev, in_stride, n, w_dev, w_stride, w_clip_stride, h_dev, h_stride, h_clip_stride, fixed, iterations, groups=None,
                        n_groups=0, stems=None, out_stride=0):
         """DeviceBuffers or device addresses; groups: None (a fit only) or `components` ints in -1..n_groups-1.  Asynchronous."""
         g = None if groups is None else (C.c_int * self.components)(*[int(v) for v in groups])
-        _ck(load().zen_hip_nmf_process_device(self._h, _ptr(in_dev), in_stride, n, _ptr(w_dev), w_stride, w_clip_stride, _ptr(h_dev), h_stride,
-                                              h_clip_stride, fixed, iterations, g, n_groups, _ptr(stems), out_stride))
+        _ck(self._L.zen_hip_nmf_process_device(self._h, _ptr(in_dev), in_stride, n, _ptr(w_dev), w_stride, w_clip_stride, _ptr(h_dev), h_stride,
+                                               h_clip_stride, fixed, iterations, g, n_groups, _ptr(stems), out_stride))
 
     def run(self, x, W, H=None, fixed=0, iterations=ITERATIONS, groups=None, n_groups=0, seed=0):
         """x: float32, (n,) for one clip or (n_clips, n).  W: (K, F) -- one dictionary for every clip, which needs fixed == K
         -- or (n_clips, K, F); H: (n_clips, K, m), or None for zen_hip_nmf_init(seed + 1) on every clip.  Returns (W, H,
         stems): copies after `iterations`, stems (n_groups, n_clips, n) or None without groups; for a one-dimensional x the
         clip axis is dropped.  Synchronous."""
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        one = x.ndim == 1
-        x = x.reshape(self.n_clips, -1)
+        x, one = _addon.clips(x, self.n_clips)
         n = x.shape[1]
         m, K, F = n_frames(n, self.nfft), self.components, self.bins
         W = np.array(W, dtype=np.float32, order="C")
@@ -152,18 +114,11 @@ class Nmf:
         H = H.reshape(self.n_clips, K, m)
         g = None if groups is None else (C.c_int * K)(*[int(v) for v in groups])
         stems = np.empty((n_groups, self.n_clips, n), np.float32) if groups is not None else None
-        _ck(load().zen_hip_nmf_process_host(self._h, x.ctypes.data, n, n, W.ctypes.data, F, 0 if shared else K * F, H.ctypes.data, m, K * m, fixed,
-                                            iterations, g, n_groups, stems.ctypes.data if stems is not None else None, n))
+        _ck(self._L.zen_hip_nmf_process_host(self._h, x.ctypes.data, n, n, W.ctypes.data, F, 0 if shared else K * F, H.ctypes.data, m, K * m, fixed,
+                                             iterations, g, n_groups, stems.ctypes.data if stems is not None else None, n))
         if one:
             return W.reshape(K, F), H[0], None if stems is None else stems[:, 0]
         return W, H, stems
-
-    def profile(self, enable=True):
-        _ck(load().zen_hip_nmf_profile(self._h, int(bool(enable))))
-
-    def profile_get(self):
-        """{kernel: {"ms", "bytes", "launches"}} since the last call; synchronises."""
-        return _addon.profile_get(_ck, load().zen_hip_nmf_profile_get, self._h, KERNELS)
 
 
 def _clip(x):

@@ -17,6 +17,7 @@ import ctypes as C
 import numpy as np
 
 from . import _addon
+from ._addon import _f, _i, _sz, _vp
 from . import lib as _zl
 
 PEAK, GAIN = 0, 1
@@ -29,7 +30,6 @@ class _HostStats(C.Structure):
 
 
 # every symbol zen_amd/pcm/zen_hip_pcm.h declares: (name, restype, argtypes)
-_vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
 _pf = C.POINTER(C.c_float)
 SYMBOLS = [
     ("zen_hip_pcm_last_error", C.c_char_p, []),
@@ -49,13 +49,8 @@ SYMBOLS = [
     ("zen_hip_pcm_hpri_process_fmt", _i, [_vp, _i, _vp, _i, _sz, _i, _vp, _vp, _vp, _i, _f, _pf, _sz]),
 ]
 
-def load():
-    """Load libzen_hip_pcm.so, building it first where it is absent (_addon.load).  Raises if that fails."""
-    return _addon.load("pcm", SYMBOLS)
-
-
-def _ck(rc):
-    _addon.check(rc, load().zen_hip_pcm_last_error)
+_lib = _addon.Library("pcm", SYMBOLS)
+load, _ck = _lib.load, _lib.check
 
 
 def _handle(engine):
@@ -200,7 +195,7 @@ def host_stats():
     """What the last host-to-host call of this thread did: pieces, pinned or not, setup / tail / total ms."""
     st = _HostStats()
     _ck(load().zen_hip_pcm_host_stats_get(C.byref(st)))
-    return {k: getattr(st, k) for k, _ in _HostStats._fields_}
+    return _addon.as_dict(st)
 
 
 def release(engine):

@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _addon
+from ._addon import _f, _i, _pd, _pull, _sz, _vp
 from . import lib as _zl
 
 KERNELS = ("pad", "fft_forward", "power", "fft_inverse", "pick")
@@ -20,8 +21,6 @@ class Stats(C.Structure):
 
 
 # every symbol zen_amd/pitch/zen_hip_pitch.h declares: (name, restype, argtypes)
-_vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
-_pd, _pull = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
 SYMBOLS = [
     ("zen_hip_pitch_last_error", C.c_char_p, []),
     ("zen_hip_pitch_version", C.c_char_p, []),
@@ -35,46 +34,22 @@ SYMBOLS = [
     ("zen_hip_pitch_profile_get", _i, [_vp, _pd, _pull, _pull]),
 ]
 
-def load():
-    """Load libzen_hip_pitch.so, building it first where it is absent (_addon.load).  Raises if that fails."""
-    return _addon.load("pitch", SYMBOLS)
+_lib = _addon.Library("pitch", SYMBOLS, kernels=KERNELS, stats=Stats)
+load, _ck, _ptr = _lib.load, _lib.check, _addon.ptr
 
 
-def _ck(rc):
-    _addon.check(rc, load().zen_hip_pitch_last_error)
-
-
-def _ptr(b):
-    """a DeviceBuffer, a raw device address or None"""
-    return getattr(b, "ptr", b)
-
-
-class Pitch:
+class Pitch(_addon.Handle):
     """zen_hip_pitch_t: chunks of n samples of n_streams rows per call."""
+    _lib = _lib
 
     def __init__(self, fs, n=4096, n_streams=1, max_chunks=0):
-        h = C.c_void_p()
-        _ck(load().zen_hip_pitch_create(fs, n, n_streams, max_chunks, C.byref(h)))
-        self._h = h.value
+        self._create(fs, n, n_streams, max_chunks)
         self.fs, self.n, self.n_streams = fs, n, n_streams
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            load().zen_hip_pitch_destroy(self._h)
-            self._h = None
-
-    def set_stream(self, stream):
-        _ck(load().zen_hip_pitch_set_stream(self._h, stream))
-
-    def stats(self):
-        st = Stats()
-        _ck(load().zen_hip_pitch_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in Stats._fields_}
 
     def run_device(self, in_dev, in_stride, n_chunks, step=None, pitch=None, period=None, clarity=None, nsdf=None, out_stride=0):
         """DeviceBuffers or device addresses (ints, e.g. DeviceBuffer.offset(k)).  Asynchronous on the handle's stream."""
-        _ck(load().zen_hip_pitch_run_device(self._h, _ptr(in_dev), in_stride, n_chunks, self.n if step is None else step, _ptr(pitch),
-                                            _ptr(period), _ptr(clarity), _ptr(nsdf), out_stride))
+        _ck(self._L.zen_hip_pitch_run_device(self._h, _ptr(in_dev), in_stride, n_chunks, self.n if step is None else step, _ptr(pitch),
+                                             _ptr(period), _ptr(clarity), _ptr(nsdf), out_stride))
 
     def n_chunks(self, samples, step=None):
         step = self.n if step is None else step
@@ -92,17 +67,10 @@ class Pitch:
         cnt = self.n_chunks(m, step)
         outs = [np.empty((self.n_streams, cnt), np.float32) for _ in range(3)]
         rows = np.empty((self.n_streams, cnt, self.n), np.float32) if nsdf else None
-        _ck(load().zen_hip_pitch_run_host(self._h, x.ctypes.data if cnt else None, m, cnt, step, *(o.ctypes.data if cnt else None for o in outs),
-                                          rows.ctypes.data if nsdf and cnt else None, cnt))
+        _ck(self._L.zen_hip_pitch_run_host(self._h, x.ctypes.data if cnt else None, m, cnt, step, *(o.ctypes.data if cnt else None for o in outs),
+                                           rows.ctypes.data if nsdf and cnt else None, cnt))
         res = outs + ([rows] if nsdf else [])
         return tuple(r[0] if one else r for r in res)
-
-    def profile(self, enable=True):
-        _ck(load().zen_hip_pitch_profile(self._h, int(bool(enable))))
-
-    def profile_get(self):
-        """{"pad" | "fft_forward" | "power" | "fft_inverse" | "pick": {"ms", "bytes", "launches"}} since the last call; synchronises."""
-        return _addon.profile_get(_ck, load().zen_hip_pitch_profile_get, self._h, KERNELS)
 
 
 class HprTracker:

@@ -11,13 +11,12 @@ import ctypes as C
 import numpy as np
 
 from . import _addon
+from ._addon import _f, _i, _pd, _psz, _pull, _sz, _vp
 from . import lib as _zl
 
 KERNELS = ("pack", "splice", "trim")
 
 # every symbol zen_amd/ragged/zen_hip_ragged.h declares: (name, restype, argtypes)
-_vp, _sz, _i, _f = C.c_void_p, C.c_size_t, C.c_int, C.c_float
-_psz, _pd, _pull = C.POINTER(C.c_size_t), C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
 SYMBOLS = [
     ("zen_hip_ragged_last_error", C.c_char_p, []),
     ("zen_hip_ragged_version", C.c_char_p, []),
@@ -34,13 +33,8 @@ SYMBOLS = [
     ("zen_hip_ragged_profile_get_engine", _i, [_vp, _i, _pd, _pull]),
 ]
 
-def load():
-    """Load libzen_hip_ragged.so, building it first where it is absent (_addon.load).  Raises if that fails."""
-    return _addon.load("ragged", SYMBOLS)
-
-
-def _ck(rc):
-    _addon.check(rc, load().zen_hip_ragged_last_error, (_zl.E_HOPS_NOT_DIVISIBLE,))
+_lib = _addon.Library("ragged", SYMBOLS, (_zl.E_HOPS_NOT_DIVISIBLE,), KERNELS)
+load, _ck = _lib.load, _lib.check
 
 
 def _lens(lens, n_clips):
@@ -48,39 +42,30 @@ def _lens(lens, n_clips):
     return (C.c_size_t * n_clips)(*[int(n) for n in lens])
 
 
-class Ragged:
+class Ragged(_addon.Profiled, _addon.EngineProfiled):
     """zen_hip_ragged_t: HPRIOffline on n_clips clips of unequal length per call."""
+    _lib = _lib
 
     def __init__(self, fs, hop_h=4096, hop_p=256, beta_h=2.0, beta_p=2.0, nocopybord=False, n_clips=1):
-        h = C.c_void_p()
-        _ck(load().zen_hip_ragged_create(fs, hop_h, hop_p, beta_h, beta_p, int(nocopybord), n_clips, C.byref(h)))
-        self._h = h.value
+        self._create(fs, hop_h, hop_p, beta_h, beta_p, int(nocopybord), n_clips)
         self.n_clips = n_clips
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            load().zen_hip_ragged_destroy(self._h)
-            self._h = None
-
     def use_sse_filter(self):
-        _ck(load().zen_hip_ragged_use_sse_filter(self._h))
+        _ck(self._L.zen_hip_ragged_use_sse_filter(self._h))
 
     def use_soft_mask(self):
-        _ck(load().zen_hip_ragged_use_soft_mask(self._h))
-
-    def set_stream(self, stream):
-        _ck(load().zen_hip_ragged_set_stream(self._h, stream))
+        _ck(self._L.zen_hip_ragged_use_soft_mask(self._h))
 
     def hop_counts(self, max_len):
         a, b = C.c_size_t(), C.c_size_t()
-        _ck(load().zen_hip_ragged_hop_counts(self._h, max_len, C.byref(a), C.byref(b)))
+        _ck(self._L.zen_hip_ragged_hop_counts(self._h, max_len, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def process_device(self, audio_dev, lens, stride, harm=None, perc=None, out_stride=None):
         """Device pointers (ints, e.g. DeviceBuffer.ptr): row c of audio_dev holds lens[c] samples; each output row gets them
         followed by zeros up to max(lens).  Asynchronous on the handle's stream."""
         out_stride = stride if out_stride is None else out_stride
-        _ck(load().zen_hip_ragged_process_device(self._h, audio_dev, _lens(lens, self.n_clips), stride, harm, perc, out_stride))
+        _ck(self._L.zen_hip_ragged_process_device(self._h, audio_dev, _lens(lens, self.n_clips), stride, harm, perc, out_stride))
 
     def process(self, clips, want=(True, True)):
         """clips: n_clips float32 arrays of any lengths (zero included).  Returns (list_harm, list_perc): per clip an array
@@ -94,19 +79,8 @@ class Ragged:
             if arrays is None:
                 return None
             return (C.c_void_p * n)(*[a.ctypes.data if a.size else None for a in arrays])
-        _ck(load().zen_hip_ragged_process_host(self._h, ptrs(clips), _lens([c.size for c in clips], n), ptrs(outs[0]), ptrs(outs[1])))
+        _ck(self._L.zen_hip_ragged_process_host(self._h, ptrs(clips), _lens([c.size for c in clips], n), ptrs(outs[0]), ptrs(outs[1])))
         return outs[0], outs[1]
-
-    def profile(self, enable=True):
-        _ck(load().zen_hip_ragged_profile(self._h, int(bool(enable))))
-
-    def profile_get(self):
-        """{"pack" | "splice" | "trim": {"ms", "bytes", "launches"}} since the last call; synchronises."""
-        return _addon.profile_get(_ck, load().zen_hip_ragged_profile_get, self._h, KERNELS)
-
-    def profile_get_engine(self):
-        """The engines' per-class kernel times, as HPRIOffline.profile_get_all."""
-        return _addon.profile_get_engine(_ck, load().zen_hip_ragged_profile_get_engine, self._h)
 
 
 def plan_groups(lengths, group):

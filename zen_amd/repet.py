@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _addon
+from ._addon import _d, _f, _i, _pd, _psz, _pull, _sz, _vp
 
 KERNELS = ("frame", "fft", "magnitude", "lag_rows", "lag_fft", "power", "braw", "median", "mask", "ifft", "overlap_add")
 TABLE_WINDOW, TABLE_DIVISOR = range(2)
@@ -22,8 +23,6 @@ class Stats(C.Structure):
 
 
 # every symbol zen_amd/repet/zen_hip_repet.h declares: (name, restype, argtypes)
-_vp, _sz, _i, _f, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double
-_pd, _pull, _psz = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong), C.POINTER(C.c_size_t)
 SYMBOLS = [
     ("zen_hip_repet_last_error", C.c_char_p, []),
     ("zen_hip_repet_version", C.c_char_p, []),
@@ -42,30 +41,9 @@ SYMBOLS = [
     ("zen_hip_repet_table", _i, [_sz, _i, _vp, _sz]),
 ]
 
-
-def load():
-    """Load libzen_hip_repet.so, building it first where it is absent (_addon.load).  Raises if that fails."""
-    return _addon.load("repet", SYMBOLS)
-
-
-def _ck(rc):
-    _addon.check(rc, load().zen_hip_repet_last_error)
-
-
-def _ptr(b):
-    """a DeviceBuffer, a raw device address or None"""
-    return getattr(b, "ptr", b)
-
-
-def n_frames(n, nfft):
-    return -(-n // (nfft // 2)) + 1
-
-
-def table(nfft, which):
-    """the window (nfft values) or the overlap divisor (nfft / 2 values) as a float32 array; needs no device"""
-    out = np.empty(nfft if which == TABLE_WINDOW else nfft // 2, np.float32)
-    _ck(load().zen_hip_repet_table(nfft, which, out.ctypes.data, out.size))
-    return out
+_lib = _addon.Library("repet", SYMBOLS, kernels=KERNELS, stats=Stats)
+load, _ck, _ptr = _lib.load, _lib.check, _addon.ptr
+n_frames, table = _addon.n_frames, _lib.stft_table
 
 
 def find_period(braw, jmin, jmax):
@@ -81,32 +59,18 @@ def segment_median_device(v_dev, m, bins, v_stride, period, s_dev, s_stride, str
     _ck(load().zen_hip_repet_segment_median_device(_ptr(v_dev), m, bins, v_stride, period, _ptr(s_dev), s_stride, stream))
 
 
-class Repet:
+class Repet(_addon.Handle):
     """zen_hip_repet_t: n_clips clips of up to max_samples samples per call, each with a period of its own"""
+    _lib = _lib
 
     def __init__(self, fs, nfft=2048, n_clips=1, max_samples=1 << 20, tmin_s=None, tmax_s=None, highpass_hz=None):
-        h = C.c_void_p()
-        _ck(load().zen_hip_repet_create(fs, nfft, n_clips, max_samples, C.byref(h)))
-        self._h = h.value
+        self._create(fs, nfft, n_clips, max_samples)
         self.fs, self.nfft, self.hop, self.n_clips, self.max_samples = fs, nfft, nfft // 2, n_clips, max_samples
         if tmin_s is not None or tmax_s is not None or highpass_hz is not None:
             self.set_params(0.8 if tmin_s is None else tmin_s, 8.0 if tmax_s is None else tmax_s, 100.0 if highpass_hz is None else highpass_hz)
 
-    def __del__(self):
-        if getattr(self, "_h", None):
-            load().zen_hip_repet_destroy(self._h)
-            self._h = None
-
-    def set_stream(self, stream):
-        _ck(load().zen_hip_repet_set_stream(self._h, stream))
-
     def set_params(self, tmin_s=0.8, tmax_s=8.0, highpass_hz=100.0):
-        _ck(load().zen_hip_repet_set_params(self._h, tmin_s, tmax_s, highpass_hz))
-
-    def stats(self):
-        st = Stats()
-        _ck(load().zen_hip_repet_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in Stats._fields_}
+        _ck(self._L.zen_hip_repet_set_params(self._h, tmin_s, tmax_s, highpass_hz))
 
     def _periods(self, periods):
         if periods is None:
@@ -121,37 +85,28 @@ class Repet:
         used = (C.c_size_t * self.n_clips)()
         m = n_frames(n, self.nfft)
         b = np.full((self.n_clips, m), np.nan, np.float32) if braw else None
-        _ck(load().zen_hip_repet_separate_device(self._h, _ptr(in_dev), in_stride, n, self._periods(periods), _ptr(background), _ptr(foreground),
-                                                 out_stride, used, b.ctypes.data if braw else None, m))
+        _ck(self._L.zen_hip_repet_separate_device(self._h, _ptr(in_dev), in_stride, n, self._periods(periods), _ptr(background), _ptr(foreground),
+                                                  out_stride, used, b.ctypes.data if braw else None, m))
         return (list(used), b) if braw else list(used)
 
     def beat_spectrum_device(self, in_dev, in_stride, n, braw_dev, braw_stride):
-        _ck(load().zen_hip_repet_beat_spectrum_device(self._h, _ptr(in_dev), in_stride, n, _ptr(braw_dev), braw_stride))
+        _ck(self._L.zen_hip_repet_beat_spectrum_device(self._h, _ptr(in_dev), in_stride, n, _ptr(braw_dev), braw_stride))
 
     def run(self, x, periods=None, background=True, foreground=True, braw=False):
         """x: float32, (n,) for one clip or (n_clips, n).  Returns (background, foreground, periods used in frames[, braw]); an
         output that was not asked for is None.  Synchronous."""
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        one = x.ndim == 1
-        x = x.reshape(self.n_clips, -1)
+        x, one = _addon.clips(x, self.n_clips)
+        pick = _addon.pick(one)
         n = x.shape[1]
         m = n_frames(n, self.nfft)
         bg = np.empty_like(x) if background else None
         fg = np.empty_like(x) if foreground else None
         b = np.full((self.n_clips, m), np.nan, np.float32) if braw else None
         used = (C.c_size_t * self.n_clips)()
-        _ck(load().zen_hip_repet_separate_host(self._h, x.ctypes.data, n, n, self._periods(periods), bg.ctypes.data if background else None,
-                                               fg.ctypes.data if foreground else None, n, used, b.ctypes.data if braw else None, m))
-        pick = (lambda a: None if a is None else a[0]) if one else (lambda a: a)
+        _ck(self._L.zen_hip_repet_separate_host(self._h, x.ctypes.data, n, n, self._periods(periods), bg.ctypes.data if background else None,
+                                                fg.ctypes.data if foreground else None, n, used, b.ctypes.data if braw else None, m))
         res = (pick(bg), pick(fg), list(used))
         return res + (pick(b),) if braw else res
-
-    def profile(self, enable=True):
-        _ck(load().zen_hip_repet_profile(self._h, int(bool(enable))))
-
-    def profile_get(self):
-        """{kernel: {"ms", "bytes", "launches"}} since the last call; synchronises."""
-        return _addon.profile_get(_ck, load().zen_hip_repet_profile_get, self._h, KERNELS)
 
 
 def separate(x, fs, nfft=2048, period_s=None, highpass_hz=100.0):

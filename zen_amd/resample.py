@@ -12,6 +12,7 @@ import math
 import numpy as np
 
 from . import _addon
+from ._addon import _d, _i, _pd, _psz, _pull, _sz, _vp
 from . import lib as _zl
 
 KERNELS = ("expand", "fir")
@@ -26,8 +27,7 @@ class Stats(C.Structure):
 
 
 # every symbol zen_amd/resample/zen_hip_resample.h declares: (name, restype, argtypes)
-_vp, _sz, _i, _d, _ull = C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_ulonglong
-_pd, _pull, _psz = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong), C.POINTER(C.c_size_t)
+_ull = C.c_ulonglong
 SYMBOLS = [
     ("zen_hip_resample_last_error", C.c_char_p, []),
     ("zen_hip_resample_version", C.c_char_p, []),
@@ -46,19 +46,8 @@ SYMBOLS = [
     ("zen_hip_resample_ratio_for_shift", _i, [_d, _pull, _pull]),
 ]
 
-
-def load():
-    """Load libzen_hip_resample.so, building it first where it is absent (_addon.load).  Raises if that fails."""
-    return _addon.load("resample", SYMBOLS)
-
-
-def _ck(rc):
-    _addon.check(rc, load().zen_hip_resample_last_error)
-
-
-def _ptr(b):
-    """a DeviceBuffer, a raw device address or None"""
-    return getattr(b, "ptr", b)
+_lib = _addon.Library("resample", SYMBOLS, kernels=KERNELS, stats=Stats)
+load, _ck, _ptr = _lib.load, _lib.check, _addon.ptr
 
 
 # ------------------------------------------------------------------------------------------------ host arithmetic, no device
@@ -108,29 +97,15 @@ def ratio_of_rates(fs_in, fs_out):
 
 
 # ------------------------------------------------------------------------------------------------ the handle
-class Resampler:
+class Resampler(_addon.Handle):
     """zen_hip_resample_t: rows converted by num / den at one quality"""
+    _lib = _lib
 
     def __init__(self, num, den, quality=16):
-        h = C.c_void_p()
-        _ck(load().zen_hip_resample_create(num, den, quality, C.byref(h)))
-        self._h = h.value
+        self._create(num, den, quality)
         g = math.gcd(num, den)
         self.num, self.den, self.quality = num // g, den // g, quality
         self.W, self.T, _ = geometry(num, den, quality)
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            load().zen_hip_resample_destroy(self._h)
-            self._h = None
-
-    def set_stream(self, stream):
-        _ck(load().zen_hip_resample_set_stream(self._h, stream))
-
-    def stats(self):
-        st = Stats()
-        _ck(load().zen_hip_resample_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in Stats._fields_}
 
     def n_out(self, n_total):
         return n_out(self.num, self.den, n_total)
@@ -140,8 +115,8 @@ class Resampler:
 
     def run_device(self, in_dev, in_stride, in_first, in_count, n_total, out_first, out_count, out_dev, out_stride, n_rows=1):
         """device rows: DeviceBuffers or device addresses; asynchronous on the handle's stream"""
-        _ck(load().zen_hip_resample_run_device(self._h, _ptr(in_dev), in_stride, in_first, in_count, n_total, out_first, out_count, _ptr(out_dev),
-                                               out_stride, n_rows))
+        _ck(self._L.zen_hip_resample_run_device(self._h, _ptr(in_dev), in_stride, in_first, in_count, n_total, out_first, out_count, _ptr(out_dev),
+                                                out_stride, n_rows))
 
     def run(self, x):
         """host rows: float32, (n,) or (rows, n) -> (n_out,) or (rows, n_out), through zen_hip_resample_run_host; synchronous"""
@@ -150,7 +125,7 @@ class Resampler:
         x = x.reshape(1, -1) if one else x
         rows, n = x.shape
         out = np.empty((rows, self.n_out(n)), np.float32)
-        _ck(load().zen_hip_resample_run_host(self._h, x.ctypes.data, n, n, out.ctypes.data, out.shape[1], rows))
+        _ck(self._L.zen_hip_resample_run_host(self._h, x.ctypes.data, n, n, out.ctypes.data, out.shape[1], rows))
         return out[0] if one else out
 
     def pieces(self, x, cuts):
@@ -167,13 +142,6 @@ class Resampler:
             _zl.synchronize()
             out.append(d_out.download())
         return np.concatenate(out) if out else np.empty(0, np.float32)
-
-    def profile(self, enable=True):
-        _ck(load().zen_hip_resample_profile(self._h, int(bool(enable))))
-
-    def profile_get(self):
-        """{kernel: {"ms", "bytes", "launches"}} since the last call; synchronises."""
-        return _addon.profile_get(_ck, load().zen_hip_resample_profile_get, self._h, KERNELS)
 
 
 def convert(x, fs_in, fs_out, quality=16):

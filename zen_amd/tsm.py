@@ -12,6 +12,7 @@ import math
 import numpy as np
 
 from . import _addon
+from ._addon import _d, _f, _i, _pd, _psz, _pull, _sz, _vp
 from . import lib as _zl
 
 KERNELS = ("frame", "fft", "analysis", "peaks", "walk", "spectrum", "ifft", "overlap_add")
@@ -24,8 +25,6 @@ class Stats(C.Structure):
 
 
 # every symbol zen_amd/tsm/zen_hip_tsm.h declares: (name, restype, argtypes)
-_vp, _sz, _i, _f, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double
-_pd, _pull, _psz = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong), C.POINTER(C.c_size_t)
 SYMBOLS = [
     ("zen_hip_tsm_last_error", C.c_char_p, []),
     ("zen_hip_tsm_version", C.c_char_p, []),
@@ -46,19 +45,8 @@ SYMBOLS = [
     ("zen_hip_tsm_table", _i, [_sz, _i, _vp, _sz]),
 ]
 
-
-def load():
-    """Load libzen_hip_tsm.so, building it first where it is absent (_addon.load).  Raises if that fails."""
-    return _addon.load("tsm", SYMBOLS)
-
-
-def _ck(rc):
-    _addon.check(rc, load().zen_hip_tsm_last_error)
-
-
-def _ptr(b):
-    """a DeviceBuffer, a raw device address or None"""
-    return getattr(b, "ptr", b)
+_lib = _addon.Library("tsm", SYMBOLS, kernels=KERNELS, stats=Stats)
+load, _ck, _ptr = _lib.load, _lib.check, _addon.ptr
 
 
 def n_out(n, alpha):
@@ -117,52 +105,38 @@ def cs(psi):
     return got[:, 0].copy(), got[:, 1].copy()
 
 
-class Tsm:
+class Tsm(_addon.Handle):
     """zen_hip_tsm_t: n_clips clips of up to max_samples samples per call, stretched alike by up to max_alpha"""
+    _lib = _lib
 
     def __init__(self, fs, nfft=4096, nfft_ola=256, n_clips=1, max_samples=None, max_alpha=4.0):
         """max_samples None: longest_clip(nfft, nfft_ola, max_alpha), 11.9 s at 44.1 kHz with the defaults"""
-        h = C.c_void_p()
         if max_samples is None:
             max_samples = longest_clip(nfft, nfft_ola, max_alpha)
-        _ck(load().zen_hip_tsm_create(fs, nfft, nfft_ola, n_clips, max_samples, max_alpha, C.byref(h)))
-        self._h = h.value
+        self._create(fs, nfft, nfft_ola, n_clips, max_samples, max_alpha)
         self.fs, self.nfft, self.nfft_ola, self.n_clips, self.max_samples, self.max_alpha = fs, nfft, nfft_ola, n_clips, max_samples, max_alpha
-
-    def __del__(self):
-        if getattr(self, "_h", None):
-            load().zen_hip_tsm_destroy(self._h)
-            self._h = None
-
-    def set_stream(self, stream):
-        _ck(load().zen_hip_tsm_set_stream(self._h, stream))
-
-    def stats(self):
-        st = Stats()
-        _ck(load().zen_hip_tsm_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in Stats._fields_}
 
     def frames(self, n, alpha):
         return (n_out(n, alpha) - 1) // (self.nfft // 4) + 4
 
     # device rows: DeviceBuffers or device addresses; asynchronous on the handle's stream
     def pv_device(self, in_dev, in_stride, n, alpha, out_dev, out_stride):
-        _ck(load().zen_hip_tsm_stretch_pv_device(self._h, _ptr(in_dev), in_stride, n, alpha, _ptr(out_dev), out_stride))
+        _ck(self._L.zen_hip_tsm_stretch_pv_device(self._h, _ptr(in_dev), in_stride, n, alpha, _ptr(out_dev), out_stride))
 
     def ola_device(self, perc_dev, resid_dev, in_stride, n, alpha, out_dev, out_stride):
-        _ck(load().zen_hip_tsm_stretch_ola_device(self._h, _ptr(perc_dev), _ptr(resid_dev), in_stride, n, alpha, _ptr(out_dev), out_stride))
+        _ck(self._L.zen_hip_tsm_stretch_ola_device(self._h, _ptr(perc_dev), _ptr(resid_dev), in_stride, n, alpha, _ptr(out_dev), out_stride))
 
     def hp_device(self, harm_dev, perc_dev, resid_dev, in_stride, n, alpha, out_dev, out_stride):
-        _ck(load().zen_hip_tsm_stretch_hp_device(self._h, _ptr(harm_dev), _ptr(perc_dev), _ptr(resid_dev), in_stride, n, alpha, _ptr(out_dev),
-                                                 out_stride))
+        _ck(self._L.zen_hip_tsm_stretch_hp_device(self._h, _ptr(harm_dev), _ptr(perc_dev), _ptr(resid_dev), in_stride, n, alpha, _ptr(out_dev),
+                                                  out_stride))
 
     def inspect_device(self, in_dev, in_stride, n, alpha, mag=None, theta=None, owner=None, psi=None):
-        _ck(load().zen_hip_tsm_inspect_device(self._h, _ptr(in_dev), in_stride, n, alpha, _ptr(mag), _ptr(theta), _ptr(owner), _ptr(psi)))
+        _ck(self._L.zen_hip_tsm_inspect_device(self._h, _ptr(in_dev), in_stride, n, alpha, _ptr(mag), _ptr(theta), _ptr(owner), _ptr(psi)))
 
     # host rows: float32, (n,) for one clip or (n_clips, n); synchronous
     def _rows(self, x):
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        return x.ndim == 1, x.reshape(self.n_clips, -1)
+        x, one = _addon.clips(x, self.n_clips)
+        return one, x
 
     def _through_device(self, alpha, call, *stems):
         one, first = self._rows(stems[0])
@@ -192,8 +166,8 @@ class Tsm:
         assert perc.shape == harm.shape and (resid is None or resid.shape == harm.shape)
         no = n_out(n, alpha)
         out = np.empty((self.n_clips, max(no, 0)), np.float32)
-        _ck(load().zen_hip_tsm_stretch_hp_host(self._h, harm.ctypes.data, perc.ctypes.data, None if resid is None else resid.ctypes.data, n, n, alpha,
-                                               out.ctypes.data, no))
+        _ck(self._L.zen_hip_tsm_stretch_hp_host(self._h, harm.ctypes.data, perc.ctypes.data, None if resid is None else resid.ctypes.data, n, n, alpha,
+                                                out.ctypes.data, no))
         return out[0] if one else out
 
     def inspect(self, x, alpha):
@@ -207,13 +181,6 @@ class Tsm:
         _zl.synchronize()
         got = tuple(o.download().reshape(shape) for o in outs)
         return tuple(g[0] for g in got) if one else got
-
-    def profile(self, enable=True):
-        _ck(load().zen_hip_tsm_profile(self._h, int(bool(enable))))
-
-    def profile_get(self):
-        """{kernel: {"ms", "bytes", "launches"}} since the last call; synchronises."""
-        return _addon.profile_get(_ck, load().zen_hip_tsm_profile_get, self._h, KERNELS)
 
 
 def stretch_hpr(x, fs, alpha, hpr_hop=1024, beta=2.5, nfft=4096, nfft_ola=256):
